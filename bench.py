@@ -26,7 +26,13 @@ Rooflines:
 The CPU baseline is the unmodified reference binary (oracle/_ref/pt_ref) on one host
 core over a bounded sample of the same workload, its image compared bit for bit.
 
+A plain run sets up, warms up, times the K steps and prints the result line. --full adds
+the passes with runs of their own: end_to_end (cold setup + first frame + D2H, then again
+in a child process on a warm code-object cache) and cpu_baseline. --dump-outputs DIR
+writes the last timed step's frame and ray count as DIR/image.npy and DIR/rays.npy.
+
   python bench.py [--gpus N] [--steps K] [--warmup W] [--scene S] [--spp S] [--res R] [--depth D]
+                  [--full] [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -91,8 +97,14 @@ def parse():
     ap.add_argument("--batch", type=int, default=0, help="samples per accumulation batch (0 = auto)")
     ap.add_argument("--cpu-spp", type=int, default=0,
                     help="spp of the bounded CPU-baseline sample (0: per scene, ~10-30 s of CPU work)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end (cold setup + render + D2H) pass")
+    ap.add_argument("--full", action="store_true",
+                    help="also the passes beside the headline figure: the end-to-end pass (cold, and warm in a "
+                         "child process) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true",
+                    help="with --full: skip the end-to-end (cold setup + render + D2H) pass")
     ap.add_argument("--e2e-only", action="store_true",
                     help="only the end-to-end pass, its JSON on stdout (the warm-cache run bench.py starts itself)")
     return ap.parse_args()
@@ -195,6 +207,24 @@ def warm_e2e(a, rtc_dir):
         return {"error": f"{type(e).__name__}: {e}"}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, image, rays) -> None:
+    """What a caller of the timed path receives from its last step, as float32 / float64 .npy:
+    image.npy, the linear frame (rows, W, 3), bottom row first (this rank's rows under --part), and
+    rays.npy, the step's ray count. A frame over the size limit is written as a fixed, seeded
+    sample of its pixels, (n, 3) in ascending pixel order."""
+    os.makedirs(path, exist_ok=True)
+    img = image.detach().cpu().numpy().astype(np.float32, copy=False)
+    limit = (DUMP_MAX_BYTES - 4096) // (3 * img.itemsize)  # pixels; room left for rays.npy and the headers
+    if img.shape[0] * img.shape[1] > limit:
+        pick = np.sort(np.random.default_rng(1).choice(img.shape[0] * img.shape[1], size=limit, replace=False))
+        img = img.reshape(-1, 3)[pick]
+    np.save(os.path.join(path, "image.npy"), np.ascontiguousarray(img))
+    np.save(os.path.join(path, "rays.npy"), np.array([rays], dtype=np.float64))
+
+
 def make_scene(a):
     from ptamd import scenes
     if a.scene == "cornell":
@@ -217,6 +247,8 @@ def main():
     a = parse()
     if a.gpus < 1:
         die(f"--gpus {a.gpus}: need at least 1")
+    if a.steps < 1 or a.warmup < 0:
+        die(f"--steps {a.steps} --warmup {a.warmup}: need at least 1 timed step and no negative warm-up")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is not None:
         if int(env_world) != a.gpus:
@@ -287,8 +319,9 @@ def run_rank(a, rank: int, world: int, local: int, launcher: str, result_path):
     # tree + H2D, hipRTC specialisation started (render.h:115-123's build + GL upload).
     # Cold means no code-object cache either: the scene kernel's on-disk cache points at a
     # fresh directory for this process (the warm-cache pass, a child process, reuses it).
+    # A plain run has no cold pass and leaves the library's cache where it is.
     rtc_dir = None
-    if not a.e2e_only:
+    if a.full and not a.e2e_only:
         rtc_dir = tempfile.mkdtemp(prefix="pt_bench_rtc_")
         os.environ["PT_RTC_CACHE_DIR"] = rtc_dir
     scene = make_scene(a)
@@ -335,7 +368,7 @@ def run_rank(a, rank: int, world: int, local: int, launcher: str, result_path):
     # with the result copied to the host (render.h:109-152). A first frame of >= 2^28
     # paths waits for the compile; a smaller one runs the generic flat kernel meanwhile.
     e2e = None
-    if not a.no_e2e or a.e2e_only:
+    if (a.full and not a.no_e2e) or a.e2e_only:
         if world > 1:
             dist.barrier()
         t0 = time.perf_counter()
@@ -378,8 +411,9 @@ def run_rank(a, rank: int, world: int, local: int, launcher: str, result_path):
     kms, launches = 0.0, 0
     render_s, gather_s = 0.0, 0.0
     kernel_name = "?"
+    frame = None
     for i in range(a.steps):
-        st, _ = step()
+        st, frame = step()
         rays += st["rays"]
         kms += st["kernel_ms"]
         launches += st["trace_launches"]
@@ -512,7 +546,10 @@ def run_rank(a, rank: int, world: int, local: int, launcher: str, result_path):
                 out["end_to_end"]["reference_bvh_build_s"] = g["bvh_hash"]["sphere223_in_cornell"]["ref_build_s"]
             except (OSError, KeyError):
                 pass
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, (frame if frame is not None else part[: rows * W * 3]).reshape(-1, W, 3),
+                     st["rays"] if world == 1 else total_rays / a.steps)
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         log("[bench] cpu baseline (reference, 1 core) ...")
         out["cpu_baseline"] = cpu_baseline(a, scene, bvh, r, cam)
     elif rank == 0:

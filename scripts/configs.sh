@@ -27,6 +27,6 @@ declare -A C=(
 NAMES=("$@")
 if [ ${#NAMES[@]} -eq 0 ]; then NAMES=($(printf '%s\n' "${!C[@]}" | sort)); fi
 for n in "${NAMES[@]}"; do
-  timeout -k 10 600 python3 bench.py ${C[$n]} > "$OUT/$n.json" 2> "$OUT/$n.log" || { echo "$n failed"; tail -5 "$OUT/$n.log"; exit 1; }
+  timeout -k 10 600 python3 bench.py --full ${C[$n]} > "$OUT/$n.json" 2> "$OUT/$n.log" || { echo "$n failed"; tail -5 "$OUT/$n.log"; exit 1; }
   python3 -c "import json,sys; d=json.load(open(sys.argv[1])); c=d.get('cpu_baseline') or {}; e=d.get('end_to_end') or {}; print('%-22s %9.0f Mray/s  e2e %9.0f  cpu %6.2f Mray/s (%s)' % (sys.argv[2], d['value'], e.get('value', 0), c.get('value', 0), c.get('kind')))" "$OUT/$n.json" "$n"
 done

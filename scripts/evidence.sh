@@ -20,7 +20,7 @@ ARGS=("$@")
 OUT="$R/gpurun_out/ev_$TAG"
 mkdir -p "$OUT"
 if [ -n "${FULL:-}" ]; then
-  (cd "$R" && timeout -k 10 900 python3 bench.py "${ARGS[@]}" > "$OUT/bench.json" 2> "$OUT/bench.log") \
+  (cd "$R" && timeout -k 10 900 python3 bench.py --full "${ARGS[@]}" > "$OUT/bench.json" 2> "$OUT/bench.log") \
     || { echo "bench failed"; tail -20 "$OUT/bench.log"; exit 1; }
   tail -c 600 "$OUT/bench.json"
 fi

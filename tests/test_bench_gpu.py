@@ -1,12 +1,16 @@
 """bench.py's one-line JSON contract on the GPU (the driver parses this line): a short Cornell
 run (the headline workload's scene, resolution and depth at 40 spp) with its CPU baseline and
-end-to-end passes, checked for every field the contract names and for the values' sanity."""
+end-to-end passes (--full), checked for every field the contract names and for the values' sanity;
+and a plain run, which does neither pass and writes its last frame with --dump-outputs."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+
+from conftest import load_golden
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -17,7 +21,7 @@ def test_bench_line_contract():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--spp", "40", "--steps", "2", "--warmup", "1",
-                        "--cpu-spp", "1"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+                        "--cpu-spp", "1", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout  # exactly one JSON line on stdout
@@ -49,3 +53,35 @@ def test_bench_line_contract():
         assert k in e, k
     assert 0 < e["value_with_device_init"] < e["value"]
     assert "error" not in e["warm"] and e["warm"]["value"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_last_frame(tmp_path):
+    """Without --full the line has the headline fields and neither extra pass, --steps sets the
+    number of timed steps, and --dump-outputs writes the frame a caller of the timed path gets:
+    at the golden fixture's size it is that image bit for bit, with the step's ray count."""
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--res", "64", "--spp", "16",
+                        "--depth", "5", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)], cwd=ROOT, env=env,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "Mray/s" and d["dtype"] == "f32"
+    assert "end_to_end" not in d and d["cpu_baseline"] is None
+    assert len([l for l in r.stderr.splitlines() if l.startswith("[bench] step ")]) == 3
+    assert d["value"] > 0 and d["ms_per_step"] > 0
+    assert abs(d["rays_per_step"] / (d["ms_per_step"] * 1e-3) / 1e6 - d["value"]) < 1e-6 * d["value"]
+    assert sorted(p.name for p in out.iterdir()) == ["image.npy", "rays.npy"]
+    img = np.load(out / "image.npy", allow_pickle=False)
+    ref = load_golden("cornell_64_s16_d5")
+    assert img.dtype == np.float32 and img.shape == ref.shape == (64, 64, 3)
+    assert np.array_equal(img.view(np.uint32), ref.view(np.uint32))
+    rays = np.load(out / "rays.npy", allow_pickle=False)
+    assert rays.dtype == np.float64 and rays.tolist() == [d["rays_per_step"]]
