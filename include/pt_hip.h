@@ -9,6 +9,9 @@
  *   pt_render_f32 / pt_ctx_render   <- render_cpu()  render.h:62-104 (loop 80-88)
  *                                     render_gpu()  render.h:109-152 (tile loop 128-139)
  *                                     trace()       render.h:36-61
+ *   pt_bvh_intersect / pt_ctx_intersect <- BVH::intersect() bvh.h:156-183 (batched; closest and any hit)
+ *   pt_ctx_render_aov                <- Camera::get_ray camera.h:63-73 + BVH::intersect + Triangle::normal
+ *                                       triangle.h:45-49 (the first hit of a sample, per pixel)
  *   pt_bvh_build                     <- BVH::build()  bvh.h:79-155 (find_best_axis 48-78)
  *   pt_camera_init                   <- Camera::Camera() camera.h:33-61
  *   pt_sample_seed                   <- rng.h:32 global LCG (stream policy, see below)
@@ -263,6 +266,67 @@ int pt_ctx_render_progressive(pt_ctx* ctx, const pt_camera* cam, const pt_params
  * pt_image_to_rgb8 of the linear image. Requires gamma > 0. */
 int pt_ctx_render_rgb8(pt_ctx* ctx, const pt_camera* cam, const pt_params* params, float gamma, int flip,
                        uint8_t* out, int out_is_device, pt_stats* stats);
+
+/* ---- ray queries and first-hit AOVs (BVH::intersect, bvh.h:156-183) ----------
+ * The answer for a ray (o, d) is what BVH::intersect returns on the scene's BVH: nodes popped
+ * LIFO (right child first), AABB::intersect_inv with inv = 1 / d, a leaf's triangles in tri_idx
+ * order, the winner replaced only when t_ < t, t starting at 1e30f. Result: the index into the
+ * caller's triangle array (tri_idx[i], -1 for a miss) and t (1e30f for a miss). The walk defines
+ * the answer (ties, triangles whose box the slab test misses), for any float in o and d.
+ * Rays are two arrays of n * 3 floats: origins and (unnormalised) directions. */
+#define PT_QUERY_CLOSEST 0
+#define PT_QUERY_ANY 1           /* occlusion: out[i] = 1 iff the closest hit's t < tmax[i] (strict) */
+
+/* The reference walk on the host over the caller's own arrays (no device needed). The scene is
+ * validated as by pt_scene_validate on every call, so pass rays in batches. n == 0: PT_OK. */
+int pt_bvh_intersect(const pt_scene* scene, const float* origins, const float* dirs, int64_t n,
+                     float* t_out, int32_t* tri_out);
+
+/* Statistics of one query or AOV call. */
+typedef struct pt_query_stats {
+    uint64_t rays;               /* rays traced (AOV: pixels of the part)                       */
+    uint64_t hits;               /* rays with a hit (PT_QUERY_ANY: occluded rays)               */
+    double kernel_ms;            /* sum of the kernel durations (HIP events)                    */
+    double total_ms;             /* end-to-end wall time of the call                            */
+    int32_t launches;            /* kernel launches                                             */
+    int32_t lds_scene;           /* 1: nodes and triangles staged in LDS; 0: read through L1/L2 */
+    int32_t lds_stack;           /* 1: traversal stack rows in LDS; 0: in a global buffer       */
+} pt_query_stats;
+
+/* Closest hit or occlusion for n rays on the context's scene (the binary child-pair walk for
+ * every scene). PT_QUERY_CLOSEST: t_out[i] and out[i] (triangle or -1), both required.
+ * PT_QUERY_ANY: out[i] = 0 / 1, t_out ignored; tmax (n floats) may be NULL = 1e30f for every
+ * ray. is_device != 0: origins, dirs, tmax, t_out and out are DEVICE pointers on the context's
+ * device (read and written in place), otherwise host pointers. n == 0 is PT_OK and launches
+ * nothing; large n is cut into several launches. The call returns after the results are
+ * complete (the context's stream is synchronised) and leaves a progressive sum as it is. */
+int pt_ctx_intersect(pt_ctx* ctx, const float* origins, const float* dirs, int64_t n, int mode,
+                     const float* tmax, float* t_out, int32_t* out, int is_device, pt_query_stats* stats);
+
+/* First-hit channels of one sample; every pointer is optional (NULL = skipped). Per pixel, rows
+ * in pt_ctx_render's order for the partition:
+ *   t        1 float   hit t, 1e30f for a miss
+ *   tri      1 int32   index into the caller's triangles, -1 for a miss
+ *   normal   3 floats  Triangle::normal(ray_d, .) (triangle.h:45-49), +0 for a miss
+ *   albedo   3 floats  material.color, +0 for a miss
+ *   emission 3 floats  material.emit_color, +0 for a miss
+ *   ray      6 floats  o.xyz, d.xyz of the camera ray (hit or miss) */
+typedef struct pt_aov {
+    float* t;
+    int32_t* tri;
+    float* normal;
+    float* albedo;
+    float* emission;
+    float* ray;
+} pt_aov;
+
+/* The first hit of sample `sample` of every pixel of this part: the ray pt_ctx_render starts for
+ * that sample (LCG state pt_sample_seed(h*W + w, sample, params->seed), Camera::get_ray) and its
+ * BVH::intersect answer. params gives seed and partition; spp, depth and the batch fields are
+ * ignored. out_is_device != 0: the channel pointers are device pointers. Synchronous, and
+ * leaves a progressive sum as it is. */
+int pt_ctx_render_aov(pt_ctx* ctx, const pt_camera* cam, const pt_params* params, int32_t sample,
+                      const pt_aov* out, int out_is_device, pt_query_stats* stats);
 
 /* Number of rows of part `part_index` for the given partition. */
 int32_t pt_part_rows(int32_t res_y, int32_t part_index, int32_t part_count, int32_t band_rows);

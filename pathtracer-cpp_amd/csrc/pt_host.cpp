@@ -884,9 +884,11 @@ int pack_scene(const pt_scene* s, PackedScene& out) {
             if (!(fabsf(s->verts[i]) < 0x1p60f)) out.coords_small = false;
         out.tris.resize(3 * (size_t)nt);
         out.mats.resize(2 * (size_t)nt);
+        out.rank_tri.resize((size_t)nt);
         for (int i = 0; i < nt; i++) {
             const int pos = rank_pos[i];
             const int t = s->tri_idx[i];
+            out.rank_tri[pos] = t;
             const float* v = s->verts + 9 * (size_t)t;
             const v3 v1{v[0], v[1], v[2]}, v2{v[3], v[4], v[5]}, v3_{v[6], v[7], v[8]};
             const v3 e1 = sub(v2, v1), e2 = sub(v3_, v1);
@@ -1031,6 +1033,53 @@ int pt_scene_info(const pt_scene* scene, int32_t* info, int32_t n) {
                                         ps.num_wide ? (ps.wide_compact ? 48 : 64) : 0};
     for (int32_t i = 0; i < n && i < PT_SCENE_INFO_N; i++) info[i] = v[i];
     return PT_SCENE_INFO_N;
+}
+
+// BVH::intersect (bvh.h:156-183) over the caller's own arrays, one ray after the other: the
+// explicit LIFO of node indices (left pushed, then right, so right is popped first), the slab
+// test with inv = 1 / d, a leaf's triangles in tri_idx order, strict t_ < t.
+int pt_bvh_intersect(const pt_scene* scene, const float* origins, const float* dirs, int64_t n, float* t_out,
+                     int32_t* tri_out) {
+    if (n < 0) return set_error(PT_E_ARG, "pt_bvh_intersect: n = %lld is negative", (long long)n);
+    PackedScene ps;
+    const int rc = pack_scene(scene, ps);  // pt_scene_validate's checks: the walk below cannot leave the arrays
+    if (rc) return rc;
+    if (n == 0) return PT_OK;
+    if (!origins || !dirs || !t_out || !tri_out) return set_error(PT_E_ARG, "pt_bvh_intersect: NULL argument");
+    std::vector<int32_t> stack;
+    stack.reserve((size_t)ps.stack_size + 1);
+    for (int64_t r = 0; r < n; r++) {
+        const float* po = origins + 3 * r;
+        const float* pd = dirs + 3 * r;
+        const v3 o{po[0], po[1], po[2]}, d{pd[0], pd[1], pd[2]};
+        const v3 inv{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
+        int32_t ret = -1;
+        float t = 1e30f;
+        stack.assign(1, 0);
+        while (!stack.empty()) {
+            const pt_bvh_node& cur = scene->nodes[stack.back()];
+            stack.pop_back();
+            if (!slab_hit(v3{cur.lb[0], cur.lb[1], cur.lb[2]}, v3{cur.rt[0], cur.rt[1], cur.rt[2]}, o, inv)) continue;
+            if (cur.left == -1 && cur.right == -1) {
+                for (int i = cur.tri_start; i <= cur.tri_end; i++) {
+                    const int32_t ti = scene->tri_idx[i];
+                    const float* v = scene->verts + 9 * (size_t)ti;
+                    const v3 v1{v[0], v[1], v[2]};
+                    float t_;
+                    if (tri_hit(v1, sub(v3{v[3], v[4], v[5]}, v1), sub(v3{v[6], v[7], v[8]}, v1), o, d, t_) && t_ < t) {
+                        t = t_;
+                        ret = ti;
+                    }
+                }
+            } else {
+                stack.push_back(cur.left);
+                stack.push_back(cur.right);
+            }
+        }
+        t_out[r] = t;
+        tri_out[r] = ret;
+    }
+    return PT_OK;
 }
 
 // Test hook: FNV-1a (64-bit) of every array and scalar pack_scene produces, so a change to the

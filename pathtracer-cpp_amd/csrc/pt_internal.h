@@ -90,6 +90,8 @@ constexpr int kPairQueueMin = 256;  // shortest flat pair queue (entries per wav
 
 struct PackedScene {
     std::vector<f4> nodes, tris, mats, leaves, wide, wtris, nrm, umats;
+    std::vector<int32_t> rank_tri;  // rank position -> index into the caller's triangles (tri_idx of that
+                                    // position): what BVH::intersect returns for a hit there (bvh.h:173)
     int32_t num_umats = 0;
     int32_t num_leaves = 0;
     int32_t num_wide = 0, wide_width = 0;
@@ -121,5 +123,35 @@ void* flat_fast_kernel(bool specular, bool mask32);
 int ctx_release_slabs(pt_ctx* c);
 // pt_debug_counter's context counters (pt_kernel.hip): 0 contexts created, 1 scene uploads.
 int64_t kernel_counter(int which);
+
+// ---- ray queries and first-hit AOVs (pt_query.hip; the entry points are in pt_kernel.hip) ----
+// A scene as the query kernels read it: device arrays in the layout above.
+struct QueryScene {
+    const f4* nodes;
+    const f4* tris;
+    const f4* mats;
+    const int32_t* rank_tri;
+    int32_t num_nodes, num_tris, tree_depth;
+};
+// Where a launch keeps the walk's stack and the scene, and its grid (query_plan).
+struct QueryPlan {
+    int lds_scene, lds_stack;  // 1: in LDS; 0: read through L1/L2 / rows in the global buffer
+    int rows;                  // stack rows per lane = max(1, tree depth)
+    int grid;                  // blocks of kBlock lanes (grid-stride over the rays or pixels)
+    size_t lds_bytes;          // dynamic LDS per block
+    size_t stack_ints;         // ints the global stack buffer must hold (0 with the stack in LDS)
+};
+// which: 0 closest hit, 1 any hit, 2 AOV. `count`: rays or pixels of the largest launch.
+int query_plan(int which, const QueryScene& sc, size_t lds_usable, int num_cus, int64_t count, QueryPlan& plan);
+// One launch over n rays (device pointers) on `stream` (a hipStream_t); no synchronisation.
+// `hits` (device): incremented by the number of rays that hit / are occluded.
+int query_launch(void* stream, const QueryScene& sc, const QueryPlan& plan, int any, const float* org, const float* dir,
+                 const float* tmax, int32_t n, float* t_out, int32_t* out, int* gstack, unsigned long long* hits,
+                 int force_exact);
+// One launch over the `rows` x cam->res[0] pixels of a part (prm: seed and partition, validated by
+// the caller); `out` holds device pointers, NULL = channel skipped.
+int aov_launch(void* stream, const QueryScene& sc, const QueryPlan& plan, const pt_camera* cam, const pt_params* prm,
+               int32_t rows, int32_t sample, const pt_aov* out, int* gstack, unsigned long long* hits,
+               int force_exact);
 
 }  // namespace pt

@@ -290,6 +290,7 @@ struct pt_ctx {
     float4* d_wtris = nullptr;
     float4* d_nrm = nullptr;    // wide path: {n.xyz, material id} per rank position
     float4* d_umats = nullptr;  // wide path: distinct materials
+    int32_t* d_rank_tri = nullptr;  // rank position -> the caller's triangle index (ray queries, AOVs)
     std::vector<f4> flat_host;  // leaf boxes for the kernel-argument table
     PackedScene meta;
     bool have_scene = false;
@@ -315,6 +316,12 @@ struct pt_ctx {
     uint8_t* d_rgb8 = nullptr;               // 8-bit output staging (pt_ctx_render_rgb8)
     size_t rgb8_bytes = 0;
     float* d_thr = nullptr;                  // quantisation thresholds, 256 floats
+    // ray queries and AOVs (pt_ctx_intersect, pt_ctx_render_aov)
+    int* d_qstack = nullptr;                 // traversal stacks, when they do not go to LDS
+    size_t qstack_ints = 0;
+    float* d_qbuf = nullptr;                 // staging of a host-pointer call's rays / channels and results
+    size_t qbuf_floats = 0;
+    unsigned long long* d_qhits = nullptr;   // hit counter of a call
     // progressive rendering: d_accum holds the running sum of prog_spp samples
     bool prog_valid = false;
     int prog_spp = 0;
@@ -1431,7 +1438,8 @@ void pt_ctx_destroy(pt_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (last) theta_table_release(c->device);  // no context left on the device to read it (re-checked there)
     for (void* p : {(void*)c->d_nodes, (void*)c->d_tris, (void*)c->d_mats, (void*)c->d_leaves, (void*)c->d_wide, (void*)c->d_wtris, (void*)c->d_nrm, (void*)c->d_umats, (void*)c->d_radiance, (void*)c->d_flags,
-                    (void*)c->d_accum, (void*)c->d_out, (void*)c->d_ctr, (void*)c->d_stamps, (void*)c->d_rgb8, (void*)c->d_thr, (void*)c->d_xstack})
+                    (void*)c->d_accum, (void*)c->d_out, (void*)c->d_ctr, (void*)c->d_stamps, (void*)c->d_rgb8, (void*)c->d_thr, (void*)c->d_xstack,
+                    (void*)c->d_rank_tri, (void*)c->d_qstack, (void*)c->d_qbuf, (void*)c->d_qhits})
         if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -1464,6 +1472,8 @@ int pt_ctx_set_scene(pt_ctx* c, const pt_scene* scene) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
+    if (c->d_rank_tri) (void)hipFree(c->d_rank_tri);
+    c->d_rank_tri = nullptr;
     c->have_scene = false;
     c->prog_valid = false;
     HIP_TRY(hipMalloc((void**)&c->d_nodes, ps.nodes.size() * sizeof(float4)));
@@ -1475,6 +1485,9 @@ int pt_ctx_set_scene(pt_ctx* c, const pt_scene* scene) {
                            c->stream));
     HIP_TRY(hipMemcpyAsync(c->d_mats, ps.mats.data(), ps.mats.size() * sizeof(float4), hipMemcpyHostToDevice,
                            c->stream));
+    HIP_TRY(hipMalloc((void**)&c->d_rank_tri, ps.rank_tri.size() * sizeof(int32_t)));
+    HIP_TRY(hipMemcpyAsync(c->d_rank_tri, ps.rank_tri.data(), ps.rank_tri.size() * sizeof(int32_t),
+                           hipMemcpyHostToDevice, c->stream));
     if (!ps.leaves.empty()) {
         HIP_TRY(hipMalloc((void**)&c->d_leaves, ps.leaves.size() * sizeof(float4)));
         HIP_TRY(hipMemcpyAsync(c->d_leaves, ps.leaves.data(), ps.leaves.size() * sizeof(float4),
@@ -1502,6 +1515,7 @@ int pt_ctx_set_scene(pt_ctx* c, const pt_scene* scene) {
     ps.nodes.clear();
     ps.tris.clear();
     ps.mats.clear();
+    ps.rank_tri.clear();
     c->has_specular = specular;
     c->dark = dark;
     c->albedo_x2 = false;
@@ -2200,6 +2214,202 @@ int pt_ctx_render_progressive(pt_ctx* c, const pt_camera* cam, const pt_params* 
     c->prog_cam = *cam;
     c->prog_prm = *prm;
     return PT_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- ray queries and first-hit AOVs
+// Entry points of the kernels in pt_query.hip. They use buffers of their own (d_qstack, d_qbuf,
+// d_qhits) and never d_accum, so a progressive sum stays valid across them.
+namespace pt {
+FastDiv fastdiv_for(uint32_t d) { return make_fastdiv(d); }  // for pt_query.hip's TraceArgs
+}
+
+namespace {
+
+constexpr int64_t kQueryChunk = 1ll << 28;      // rays per launch: 3 * i stays below 2^31 in the kernel
+constexpr int64_t kQueryHostChunk = 1ll << 22;  // rays staged at a time for a host-pointer call
+
+QueryScene query_scene(const pt_ctx* c) {
+    return QueryScene{reinterpret_cast<const f4*>(c->d_nodes), reinterpret_cast<const f4*>(c->d_tris),
+                      reinterpret_cast<const f4*>(c->d_mats), c->d_rank_tri, c->meta.num_nodes, c->meta.num_tris,
+                      c->meta.tree_depth};
+}
+
+int query_force_exact() {
+    const char* fe = hook_env("PT_FORCE_EXACT_SLAB");
+    return (fe && (*fe == '1' || *fe == '2')) ? 1 : 0;
+}
+
+// The plan's global stack (if any) and the zeroed hit counter.
+int query_buffers(pt_ctx* c, const QueryPlan& plan) {
+    if (plan.stack_ints > c->qstack_ints) {
+        if (c->d_qstack) (void)hipFree(c->d_qstack);
+        c->d_qstack = nullptr;
+        c->qstack_ints = 0;
+        HIP_TRY(hipMalloc((void**)&c->d_qstack, plan.stack_ints * sizeof(int)));
+        c->qstack_ints = plan.stack_ints;
+    }
+    if (!c->d_qhits) HIP_TRY(hipMalloc((void**)&c->d_qhits, sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(c->d_qhits, 0, sizeof(unsigned long long), c->stream));
+    return PT_OK;
+}
+
+struct EventPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~EventPair() {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+};
+
+int query_finish(pt_ctx* c, const QueryPlan& plan, uint64_t rays, double kernel_ms, int launches,
+                 std::chrono::steady_clock::time_point t_start, pt_query_stats* stats) {
+    unsigned long long hits = 0;
+    HIP_TRY(hipMemcpyAsync(&hits, c->d_qhits, sizeof(hits), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (stats) {
+        stats->rays = rays;
+        stats->hits = hits;
+        stats->kernel_ms = kernel_ms;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+        stats->launches = launches;
+        stats->lds_scene = plan.lds_scene;
+        stats->lds_stack = plan.lds_stack;
+    }
+    return PT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pt_ctx_intersect(pt_ctx* c, const float* origins, const float* dirs, int64_t n, int mode, const float* tmax,
+                     float* t_out, int32_t* out, int is_device, pt_query_stats* stats) {
+    const auto t_start = std::chrono::steady_clock::now();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!c) return set_error(PT_E_ARG, "pt_ctx_intersect: context is NULL");
+    if (mode != PT_QUERY_CLOSEST && mode != PT_QUERY_ANY) return set_error(PT_E_ARG, "pt_ctx_intersect: unknown mode %d", mode);
+    if (n < 0) return set_error(PT_E_ARG, "pt_ctx_intersect: n = %lld is negative", (long long)n);
+    if (!c->have_scene) return set_error(PT_E_ARG, "pt_ctx_intersect: no scene set");
+    if (n == 0) return PT_OK;
+    const bool any = mode == PT_QUERY_ANY;
+    if (!origins || !dirs || !out || (!any && !t_out)) return set_error(PT_E_ARG, "pt_ctx_intersect: NULL argument");
+    if (int rc0 = ctx_ready(c)) return rc0;
+    HIP_TRY(hipSetDevice(c->device));
+    const QueryScene sc = query_scene(c);
+    const int64_t chunk = std::min(n, is_device ? kQueryChunk : kQueryHostChunk);
+    QueryPlan plan;
+    int rc;
+    if ((rc = query_plan(any ? 1 : 0, sc, c->lds_usable, c->num_cus, chunk, plan))) return rc;
+    if ((rc = query_buffers(c, plan))) return rc;
+    // host pointers: one staging buffer [origins 3][dirs 3][tmax 1][t 1][out 1] x chunk
+    float *s_org = nullptr, *s_dir = nullptr, *s_tmax = nullptr, *s_t = nullptr;
+    int32_t* s_out = nullptr;
+    if (!is_device) {
+        if ((rc = ensure(&c->d_qbuf, &c->qbuf_floats, 9 * (size_t)chunk))) return rc;
+        s_org = c->d_qbuf;
+        s_dir = s_org + 3 * chunk;
+        s_tmax = s_dir + 3 * chunk;
+        s_t = s_tmax + chunk;
+        s_out = reinterpret_cast<int32_t*>(s_t + chunk);
+    }
+    EventPair ev;
+    HIP_TRY(hipEventCreate(&ev.a));
+    HIP_TRY(hipEventCreate(&ev.b));
+    double kernel_ms = 0;
+    int launches = 0;
+    for (int64_t i0 = 0; i0 < n; i0 += chunk) {
+        const int32_t m = (int32_t)std::min(chunk, n - i0);
+        const float *k_org = origins + 3 * i0, *k_dir = dirs + 3 * i0, *k_tmax = tmax ? tmax + i0 : nullptr;
+        float* k_t = t_out ? t_out + i0 : nullptr;
+        int32_t* k_out = out + i0;
+        if (!is_device) {
+            HIP_TRY(hipMemcpyAsync(s_org, k_org, 3 * sizeof(float) * (size_t)m, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(s_dir, k_dir, 3 * sizeof(float) * (size_t)m, hipMemcpyHostToDevice, c->stream));
+            if (any && tmax)
+                HIP_TRY(hipMemcpyAsync(s_tmax, k_tmax, sizeof(float) * (size_t)m, hipMemcpyHostToDevice, c->stream));
+            k_org = s_org;
+            k_dir = s_dir;
+            k_tmax = (any && tmax) ? s_tmax : nullptr;
+            k_t = s_t;
+            k_out = s_out;
+        }
+        HIP_TRY(hipEventRecord(ev.a, c->stream));
+        if ((rc = query_launch(c->stream, sc, plan, any, k_org, k_dir, any ? k_tmax : nullptr, m, k_t, k_out, c->d_qstack,
+                               c->d_qhits, query_force_exact())))
+            return rc;
+        HIP_TRY(hipEventRecord(ev.b, c->stream));
+        launches++;
+        if (!is_device) {
+            if (!any)
+                HIP_TRY(hipMemcpyAsync(t_out + i0, s_t, sizeof(float) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(out + i0, s_out, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+        }
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
+        kernel_ms += ms;
+    }
+    return query_finish(c, plan, (uint64_t)n, kernel_ms, launches, t_start, stats);
+}
+
+int pt_ctx_render_aov(pt_ctx* c, const pt_camera* cam, const pt_params* prm, int32_t sample, const pt_aov* out,
+                      int out_is_device, pt_query_stats* stats) {
+    const auto t_start = std::chrono::steady_clock::now();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!c || !cam || !prm || !out) return set_error(PT_E_ARG, "pt_ctx_render_aov: NULL argument");
+    if (sample < 0) return set_error(PT_E_ARG, "pt_ctx_render_aov: sample %d is negative", sample);
+    if (!c->have_scene) return set_error(PT_E_ARG, "pt_ctx_render_aov: no scene set");
+    const int W = cam->res[0], H = cam->res[1];
+    if (W <= 0 || H <= 0) return set_error(PT_E_ARG, "camera resolution must be positive");
+    const int parts = prm->part_count > 0 ? prm->part_count : 1;
+    const int band = prm->band_rows > 0 ? prm->band_rows : 1;
+    if (prm->part_index < 0 || prm->part_index >= parts) return set_error(PT_E_ARG, "part_index out of range");
+    const int rows = pt_part_rows(H, prm->part_index, parts, band);
+    const long long npix = (long long)rows * W;
+    if (npix > (1ll << 30)) return set_error(PT_E_ARG, "too many pixels for one part");
+    if (npix == 0) return PT_OK;
+    if (int rc0 = ctx_ready(c)) return rc0;
+    HIP_TRY(hipSetDevice(c->device));
+    const QueryScene sc = query_scene(c);
+    QueryPlan plan;
+    int rc;
+    if ((rc = query_plan(2, sc, c->lds_usable, c->num_cus, npix, plan))) return rc;
+    if ((rc = query_buffers(c, plan))) return rc;
+    // host pointers: the requested channels staged one after the other in d_qbuf
+    float* const host[6] = {out->t, reinterpret_cast<float*>(out->tri), out->normal, out->albedo, out->emission, out->ray};
+    const int width[6] = {1, 1, 3, 3, 3, 6};
+    float* dev[6];
+    if (out_is_device) {
+        for (int k = 0; k < 6; k++) dev[k] = host[k];
+    } else {
+        size_t total = 0;
+        for (int k = 0; k < 6; k++) total += host[k] ? (size_t)width[k] * npix : 0;
+        if ((rc = ensure(&c->d_qbuf, &c->qbuf_floats, total))) return rc;
+        size_t at = 0;
+        for (int k = 0; k < 6; k++) {
+            dev[k] = host[k] ? c->d_qbuf + at : nullptr;
+            at += host[k] ? (size_t)width[k] * npix : 0;
+        }
+    }
+    const pt_aov d_out{dev[0], reinterpret_cast<int32_t*>(dev[1]), dev[2], dev[3], dev[4], dev[5]};
+    EventPair ev;
+    HIP_TRY(hipEventCreate(&ev.a));
+    HIP_TRY(hipEventCreate(&ev.b));
+    HIP_TRY(hipEventRecord(ev.a, c->stream));
+    if ((rc = aov_launch(c->stream, sc, plan, cam, prm, rows, sample, &d_out, c->d_qstack, c->d_qhits, query_force_exact())))
+        return rc;
+    HIP_TRY(hipEventRecord(ev.b, c->stream));
+    if (!out_is_device)
+        for (int k = 0; k < 6; k++)
+            if (host[k])
+                HIP_TRY(hipMemcpyAsync(host[k], dev[k], sizeof(float) * (size_t)width[k] * npix, hipMemcpyDeviceToHost,
+                                       c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
+    return query_finish(c, plan, (uint64_t)npix, ms, 1, t_start, stats);
 }
 
 }  // extern "C"

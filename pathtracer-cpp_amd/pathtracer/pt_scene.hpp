@@ -182,6 +182,56 @@ struct BVH {
         built = true;
     }
 
+    // bvh.h:156-183, on the host, one ray: the triangle hit first in the reference's test order
+    // (index into `triangles`, -1 for a miss) and its t (FLOAT_INF for a miss).
+    int intersect(const vec3& ray_o, const vec3& ray_d, float& t) const {
+        const vec3 inv_ray_d = 1 / ray_d;
+        std::vector<int> stack{0};
+        int ret = -1;
+        t = FLOAT_INF;
+        while (!stack.empty()) {
+            const BVHNode& cur = nodes[stack.back()];
+            stack.pop_back();
+            if (!cur.aabb.intersect_inv(ray_o, inv_ray_d)) continue;
+            if (cur.is_leaf()) {
+                for (int i = cur.tri_start; i <= cur.tri_end; i++) {
+                    float t_;
+                    if (triangles[tri_idx[i]].intersect(ray_o, ray_d, t_) && t_ < t) {
+                        t = t_;
+                        ret = tri_idx[i];
+                    }
+                }
+            } else {
+                stack.push_back(cur.left);
+                stack.push_back(cur.right);
+            }
+        }
+        return ret;
+    }
+
+    // Extension: intersect() for n rays (o, d: n x 3 floats; t, tri: n results). On HIP device
+    // `device` when one is visible (pt_ctx_intersect: upload, one batched launch), otherwise the
+    // same walk on the host (pt_bvh_intersect). The BVH must be built. Throws on failure.
+    void intersect_batch(const float* o, const float* d, size_t n, float* t, int* tri, int device = 0) const {
+        if (!built) throw std::runtime_error("BVH::intersect_batch: BVH not built");
+        static_assert(sizeof(int) == sizeof(int32_t), "tri_idx is handed to the C ABI as int32_t");
+        const std::vector<float> v = packed_vertices();
+        const std::vector<pt_material> m = packed_materials();
+        const pt_scene sc{(int32_t)triangles.size(), v.data(), m.data(), (int32_t)nodes.size(),
+                          reinterpret_cast<const pt_bvh_node*>(nodes.data()), tri_idx.data()};
+        int rc;
+        if (pt_device_count() > 0) {
+            pt_ctx* ctx = nullptr;
+            rc = pt_ctx_create(device, &ctx);
+            if (rc == PT_OK) rc = pt_ctx_set_scene(ctx, &sc);
+            if (rc == PT_OK) rc = pt_ctx_intersect(ctx, o, d, (int64_t)n, PT_QUERY_CLOSEST, nullptr, t, tri, 0, nullptr);
+            pt_ctx_destroy(ctx);
+        } else {
+            rc = pt_bvh_intersect(&sc, o, d, (int64_t)n, t, tri);
+        }
+        if (rc != PT_OK) throw std::runtime_error(std::string("BVH::intersect_batch: ") + pt_last_error());
+    }
+
     // Wavefront OBJ + MTL import with the reference's material mapping (bvh.h:184-242):
     // illum 1 -> DIFFUSE(Kd), illum 2 -> EMIT(Ka), otherwise DIFFUSE(0.5). Polygons are
     // fan-triangulated; faces must reference a material (the reference indexes

@@ -71,6 +71,18 @@ class Triangle:
     material: Material
 
 
+def _rays(origins, directions) -> Tuple[np.ndarray, np.ndarray]:
+    o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise ValueError("origins and directions must both be (n, 3)")
+    return o, d
+
+
+def _is_tensor(x) -> bool:
+    return hasattr(x, "data_ptr")
+
+
 @dataclass
 class BVH:
     """Scene container = the reference's BVH (bvh.h:30-37): triangles + built tree."""
@@ -211,6 +223,18 @@ class BVH:
             m = mats[i]
             self.add_triangle(Triangle(tuple(v[i][0:3]), tuple(v[i][3:6]), tuple(v[i][6:9]),
                                        Material(m.type, tuple(m.color), tuple(m.emit), m.roughness)))
+
+    def intersect(self, origins, directions):
+        """BVH::intersect (bvh.h:156-183) for a batch of rays on the host (pt_bvh_intersect; no
+        device needed): origins and directions (n, 3) float32 -> (t (n,) float32, tri (n,) int32),
+        tri = index into `triangles` or -1, t = 1e30 for a miss."""
+        ref = _SceneRef(self)
+        o, d = _rays(origins, directions)
+        t = np.empty(o.shape[0], dtype=np.float32)
+        tri = np.empty(o.shape[0], dtype=np.int32)
+        check(lib().pt_bvh_intersect(C.byref(ref.s), o.ctypes.data, d.ctypes.data, o.shape[0], t.ctypes.data,
+                                     tri.ctypes.data))
+        return t, tri
 
     @classmethod
     def from_scene(cls, scene) -> "BVH":
@@ -369,6 +393,65 @@ class Renderer:
         check(lib().pt_ctx_render_rgb8(self.h, C.byref(camera.c), C.byref(prm), C.c_float(gamma), int(flip),
                                        C.c_void_p(out.data_ptr()), 1, C.byref(st)))
         return out, st.as_dict()
+
+    def intersect(self, origins, directions, any_hit: bool = False, tmax=None, out=None):
+        """Closest hit or occlusion for a batch of rays on this context's scene (pt_ctx_intersect;
+        the answer is BVH::intersect's, bvh.h:156-183). numpy (n, 3) float32 in: returns
+        ((t, tri), stats), or (occluded, stats) with any_hit (int32 0 / 1: t < tmax, tmax (n,)
+        or None = 1e30). Contiguous float32 torch tensors on this context's device go through
+        the device-pointer path: `out` = (t, tri) tensors (float32, int32), or the int32
+        `occluded` tensor with any_hit, written in place and returned."""
+        st = _lib.pt_query_stats()
+        mode = _lib.PT_QUERY_ANY if any_hit else _lib.PT_QUERY_CLOSEST
+        if _is_tensor(origins):
+            n = origins.numel() // 3
+            tens = [origins, directions] + ([tmax] if tmax is not None else [])
+            if out is None:
+                import torch
+                tri = torch.empty(n, dtype=torch.int32, device=origins.device)
+                out = tri if any_hit else (torch.empty(n, dtype=torch.float32, device=origins.device), tri)
+            outs = [out] if any_hit else list(out)
+            for x in tens + outs:
+                if not x.is_contiguous() or not x.is_cuda or x.element_size() != 4:
+                    raise ValueError("tensors must be contiguous 32-bit tensors on the context's device")
+            if directions.numel() != 3 * n or any(x.numel() != n for x in tens[2:] + outs):
+                raise ValueError("directions must hold n x 3 elements, tmax and the outputs n")
+            ptrs = [C.c_void_p(x.data_ptr()) for x in tens + outs]
+            check(lib().pt_ctx_intersect(self.h, ptrs[0], ptrs[1], n, mode, ptrs[2] if tmax is not None else None,
+                                         None if any_hit else ptrs[-2], ptrs[-1], 1, C.byref(st)))
+            return out, st.as_dict()
+        o, d = _rays(origins, directions)
+        n = o.shape[0]
+        tm = None
+        if tmax is not None:
+            tm = np.ascontiguousarray(tmax, dtype=np.float32).reshape(-1)
+            if tm.shape[0] != n:
+                raise ValueError("tmax must hold one float per ray")
+        t = np.empty(n, dtype=np.float32)
+        res = np.empty(n, dtype=np.int32)
+        check(lib().pt_ctx_intersect(self.h, o.ctypes.data, d.ctypes.data, n, mode,
+                                     tm.ctypes.data if tm is not None else None,
+                                     None if any_hit else t.ctypes.data, res.ctypes.data, 0, C.byref(st)))
+        return (res if any_hit else (t, res)), st.as_dict()
+
+    def aov(self, camera: Camera, sample: int = 0, seed: int = PT_SEED,
+            channels: Sequence[str] = _lib.pt_aov.CHANNELS, part_index: int = 0, part_count: int = 1,
+            band_rows: int = 1):
+        """First-hit channels of sample `sample` of this part's pixels (pt_ctx_render_aov): a
+        dict of (rows, W) arrays for "t" (float32) and "tri" (int32), (rows, W, 3) for
+        "normal", "albedo", "emission" and (rows, W, 6) for "ray" (o.xyz, d.xyz), rows in
+        render()'s order, + stats."""
+        W, H = camera.res
+        rows = self.part_rows(H, part_index, part_count, band_rows)
+        prm = _lib.pt_params(1, 1, seed, part_index, part_count, band_rows, 0, 0)
+        res, aov = {}, _lib.pt_aov()
+        for k in channels:
+            w = _lib.pt_aov.WIDTH[k]  # KeyError: not a channel
+            res[k] = np.empty((rows, W) if w == 1 else (rows, W, w), dtype=np.int32 if k == "tri" else np.float32)
+            setattr(aov, k, res[k].ctypes.data)
+        st = _lib.pt_query_stats()
+        check(lib().pt_ctx_render_aov(self.h, C.byref(camera.c), C.byref(prm), sample, C.byref(aov), 0, C.byref(st)))
+        return res, st.as_dict()
 
 
 def render(camera: Camera, bvh: BVH, samples: int, depth: int, seed: int = PT_SEED, device: int = 0,

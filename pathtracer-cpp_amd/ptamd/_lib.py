@@ -28,6 +28,7 @@ EXPORTED = (
     "pt_render_f32_devices", "pt_render_rgb8_devices", "pt_scene_info", "pt_debug_wide_verify",
     "pt_debug_rccl_failover", "pt_debug_rtc_cache", "pt_devices_release", "pt_debug_ctx_flags", "pt_debug_counter",
     "pt_debug_scene_dark", "pt_debug_rtc_start", "pt_debug_pack_hash",
+    "pt_bvh_intersect", "pt_ctx_intersect", "pt_ctx_render_aov",
 )
 PT_MAX_DEVICES = 16
 
@@ -78,6 +79,24 @@ class pt_stats(C.Structure):
         for k in ("device_kernel_ms", "device_render_ms", "device_rays"):
             d[k] = list(d[k])[:n]
         return d
+
+
+PT_QUERY_CLOSEST, PT_QUERY_ANY = 0, 1
+
+
+class pt_query_stats(C.Structure):
+    _fields_ = [("rays", C.c_uint64), ("hits", C.c_uint64), ("kernel_ms", C.c_double), ("total_ms", C.c_double),
+                ("launches", C.c_int32), ("lds_scene", C.c_int32), ("lds_stack", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class pt_aov(C.Structure):
+    """First-hit channels (include/pt_hip.h); a NULL pointer skips the channel."""
+    CHANNELS = ("t", "tri", "normal", "albedo", "emission", "ray")
+    WIDTH = {"t": 1, "tri": 1, "normal": 3, "albedo": 3, "emission": 3, "ray": 6}
+    _fields_ = [(k, C.c_void_p) for k in CHANNELS]
 
 
 assert C.sizeof(pt_bvh_node) == 40 and C.sizeof(pt_material) == 32
@@ -166,6 +185,10 @@ def lib() -> C.CDLL:
         L.pt_scene_info.argtypes = [C.POINTER(pt_scene), P, C.c_int32]
         L.pt_debug_wide_verify.argtypes = [C.POINTER(pt_scene), C.c_int32]
         L.pt_rtc_check.argtypes = [C.POINTER(pt_scene), C.c_char_p, C.c_size_t]
+        L.pt_bvh_intersect.argtypes = [C.POINTER(pt_scene), P, P, C.c_int64, P, P]
+        L.pt_ctx_intersect.argtypes = [P, P, P, C.c_int64, C.c_int, P, P, P, C.c_int, C.POINTER(pt_query_stats)]
+        L.pt_ctx_render_aov.argtypes = [P, C.POINTER(pt_camera), C.POINTER(pt_params), C.c_int32, C.POINTER(pt_aov),
+                                        C.c_int, C.POINTER(pt_query_stats)]
         if hasattr(L, "pt_debug_rccl_failover"):  # test hooks (absent from older builds used in A/B runs)
             L.pt_debug_rccl_failover.argtypes = [C.c_int32, C.c_int32, P]
         if hasattr(L, "pt_debug_rtc_cache"):
