@@ -1119,6 +1119,10 @@ int pt_debug_wide_verify(const pt_scene* scene, int32_t width) {
     int rc = pack_scene(scene, ps);
     if (rc) return rc;
     if (width != 4 && width != 8) return set_error(PT_E_ARG, "width must be 4 or 8");
+    // pack_scene's own conditions for a wide tree: nested boxes over a partition, an interior
+    // root (build_wide reads the root's children)
+    if (ps.num_leaves == 0 || (scene->nodes[0].left == -1 && scene->nodes[0].right == -1))
+        return set_error(PT_E_ARG, "scene has no wide tree");
     // rank positions as pack_scene computes them (LIFO walk, left pushed first)
     const int nt = scene->num_tris;
     std::vector<int32_t> rank_pos(nt, -1);

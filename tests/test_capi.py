@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import _oracle as O
+from _trees import merge_leaf_pairs as _merge_leaf_pairs
 from conftest import ROOT, load_golden, scene_for, scene_hash
 
 
@@ -456,26 +457,6 @@ def test_wide_records_keep_leaf_box_unless_triangle_aabb(pt):
     assert info["wide_nodes"] > 0 and info["wide_record_bytes"] == 64
     ref = pt._SceneRef(bvh)  # keeps the arrays alive during the call
     assert pt.lib().pt_debug_wide_verify(C.byref(ref.s), 8) == 0
-
-
-def _merge_leaf_pairs(nodes: np.ndarray, every: int = 2) -> int:
-    """Turn every `every`-th interior node whose children are both one-triangle leaves with
-    adjacent ranges into a two-triangle leaf (a tree the C ABI accepts from any builder).
-    Returns the nodes merged."""
-    merged = 0
-    for n in range(len(nodes)):
-        l, r = nodes["left"][n], nodes["right"][n]
-        if l == -1 or (n % every):
-            continue
-        kids = [l, r]
-        if all(nodes["left"][k] == -1 and nodes["right"][k] == -1 and
-               nodes["tri_start"][k] == nodes["tri_end"][k] for k in kids):
-            s0, s1 = sorted(int(nodes["tri_start"][k]) for k in kids)
-            if s1 == s0 + 1:
-                nodes["left"][n] = nodes["right"][n] = -1
-                nodes["tri_start"][n], nodes["tri_end"][n] = s0, s1
-                merged += 1
-    return merged
 
 
 def test_scene_packing_is_thread_count_independent(pt, monkeypatch):

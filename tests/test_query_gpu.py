@@ -138,6 +138,67 @@ def test_device_pointers(renderers):
     assert np.array_equal(RW.bits(to.cpu().numpy()), RW.bits(o)) and np.array_equal(RW.bits(td.cpu().numpy()), RW.bits(d))
 
 
+def _tiled(name, n, seed):
+    """n rays drawn from the scene's 1024-ray set by seeded permutations laid end to end, with
+    the known answers taken the same way (no new reference walks)."""
+    o, d, t_ref, tri_ref = RW.expected(name)
+    rng = np.random.default_rng(seed)
+    m = o.shape[0]
+    pick = np.concatenate([rng.permutation(m) for _ in range(-(-n // m))])[:n]
+    return pick, np.take(o, pick, axis=0), np.take(d, pick, axis=0), np.take(t_ref, pick), np.take(tri_ref, pick)
+
+
+def _tmax_for(t_ref, tri_ref):
+    """test_any_hit's per-ray bounds for the base ray set."""
+    n = t_ref.shape[0]
+    pick = np.random.default_rng(5).integers(4, size=n)
+    hit_choices = np.stack([F32(0.5) * t_ref, t_ref, np.nextafter(t_ref, F32(np.inf)), np.full(n, 1e30, F32)])
+    miss_choices = np.stack([np.full(n, 1.0, F32), np.full(n, 1e30, F32)])
+    return np.where(tri_ref >= 0, hit_choices[pick, np.arange(n)], miss_choices[pick % 2, np.arange(n)]).astype(F32)
+
+
+def test_grid_stride_loop_runs_twice_on_device_pointers(renderers):
+    """2^20 + 5 rays in one launch: more than the 8 blocks x 256 lanes per CU a launch can hold,
+    so lanes take a second trip round the kernel's grid-stride loop; bits, ids and the hit
+    counter against the tiled known answers."""
+    import torch
+    name = "random_3_40"
+    r, _ = renderers(name)
+    n = (1 << 20) + 5
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    assert n > 8 * cus * 256
+    _, o, d, t_ref, tri_ref = _tiled(name, n, 11)
+    dev = torch.device("cuda", 0)
+    to, td = torch.from_numpy(o).to(dev), torch.from_numpy(d).to(dev)
+    (t, tri), st = r.intersect(to, td)
+    assert st["rays"] == n and st["launches"] == 1 and st["hits"] == int((tri_ref >= 0).sum())
+    _same(t.cpu().numpy(), tri.cpu().numpy(), t_ref, tri_ref)
+    occ, st = r.intersect(to, td, any_hit=True)
+    assert np.array_equal(occ.cpu().numpy(), (tri_ref >= 0).astype(np.int32)) and st["hits"] == int((tri_ref >= 0).sum())
+
+
+def test_host_pointer_call_runs_two_chunks(renderers):
+    """2^22 + 321 rays through host pointers: pt_ctx_intersect stages 2^22 at a time, so two
+    launches; closest hit and any hit (per-ray tmax), the hit count summed over both, and the
+    second chunk's 321 answers."""
+    name = "cornell"
+    r, _ = renderers(name)
+    chunk = 1 << 22
+    n = chunk + 321
+    pick, o, d, t_ref, tri_ref = _tiled(name, n, 12)
+    (t, tri), st = r.intersect(o, d)
+    assert st["rays"] == n and st["launches"] == 2 and st["hits"] == int((tri_ref >= 0).sum())
+    _same(t[chunk:], tri[chunk:], t_ref[chunk:], tri_ref[chunk:])
+    _same(t, tri, t_ref, tri_ref)
+    assert (tri_ref[chunk:] >= 0).any() and (tri_ref[chunk:] < 0).any()
+    base = RW.expected(name)
+    tmax = np.take(_tmax_for(base[2], base[3]), pick)
+    want = (t_ref < tmax).astype(np.int32)
+    occ, st = r.intersect(o, d, any_hit=True, tmax=tmax)
+    assert st["launches"] == 2 and st["hits"] == int(want.sum()) and 0 < want[chunk:].sum() < 321
+    assert np.array_equal(occ[chunk:], want[chunk:]) and np.array_equal(occ, want)
+
+
 def _tri_normal(verts, tri, d):
     """Triangle::normal (triangle.h:45-49) in float32, linalg.h's operation order:
     edge1 x edge2, / length, then n . d < 0 ? n : -n."""
