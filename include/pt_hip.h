@@ -10,6 +10,7 @@
  *                                     render_gpu()  render.h:109-152 (tile loop 128-139)
  *                                     trace()       render.h:36-61
  *   pt_bvh_intersect / pt_ctx_intersect <- BVH::intersect() bvh.h:156-183 (batched; closest and any hit)
+ *   pt_bvh_trace / pt_ctx_trace <- trace() render.h:36-61 (batched, caller's rays)
  *   pt_ctx_render_aov                <- Camera::get_ray camera.h:63-73 + BVH::intersect + Triangle::normal
  *                                       triangle.h:45-49 (the first hit of a sample, per pixel)
  *   pt_bvh_build                     <- BVH::build()  bvh.h:79-155 (find_best_axis 48-78)
@@ -327,6 +328,48 @@ typedef struct pt_aov {
  * leaves a progressive sum as it is. */
 int pt_ctx_render_aov(pt_ctx* ctx, const pt_camera* cam, const pt_params* params, int32_t sample,
                       const pt_aov* out, int out_is_device, pt_query_stats* stats);
+
+/* ---- radiance along caller-supplied rays (trace(), render.h:36-61) ------------
+ * rgb_out[3 i ..] = (sum over s of trace(bvh, o_i, d_i, depth)) / (float)spp: the sum runs in
+ * float32 in sample order s = 0, 1, ... from +0 and is divided per channel (image.h:37-40); with
+ * spp == 1 the result is the sample itself. Sample s of ray i runs the reference's LCG from its
+ * given state; no camera draws are made (the ray is the caller's), and directions are used as
+ * given (unnormalised), exactly as trace() would. Rays are two arrays of n * 3 floats, as for
+ * pt_ctx_intersect. */
+typedef struct pt_trace_params {
+    int32_t depth;               /* trace()'s depth, 0..PT_MAX_DEPTH; 0: every result +0, no ray traced (render.h:37) */
+    int32_t spp;                 /* samples per ray, 1..(1 << 20) */
+    uint32_t seed;
+    const uint32_t* states;      /* optional, n * spp: LCG state sample s of ray i starts with, at [i * spp + s].
+                                    NULL: pt_sample_seed((uint32_t)i, s, seed), i = the ray's index in the call */
+} pt_trace_params;
+
+typedef struct pt_trace_stats {  /* 64 bytes */
+    uint64_t rays;               /* traced segments = BVH::intersect calls */
+    uint64_t paths;              /* n * spp */
+    uint64_t runaway;            /* specular rejection loops that hit the bound (0 normally) */
+    double kernel_ms;            /* sum of the trace-kernel durations (HIP events)  */
+    double reduce_ms;            /* sum of the in-order sum passes' durations       */
+    double total_ms;             /* end-to-end wall time of the call                */
+    int32_t launches;            /* trace-kernel launches                           */
+    int32_t lds_scene;           /* 1: nodes, triangles and materials staged in LDS */
+    int32_t lds_stack;           /* 1: traversal stack rows in LDS                  */
+    int32_t lds_records;         /* 1: path records in LDS; 0: in a global buffer   */
+} pt_trace_stats;
+
+/* trace() on the host over the caller's own arrays (no device needed), bit-identical to
+ * pt_ctx_trace. The scene is validated as by pt_scene_validate on every call. */
+int pt_bvh_trace(const pt_scene* scene, const float* origins, const float* dirs, int64_t n,
+                 const pt_trace_params* params, float* rgb_out, pt_trace_stats* stats);
+
+/* trace() for n rays on the context's scene (the binary child-pair walk for every scene).
+ * is_device != 0: origins, dirs, params->states and rgb_out are DEVICE pointers on the context's
+ * device (the inputs are left untouched), otherwise host pointers. n == 0 is PT_OK and launches
+ * nothing; large n * spp is cut into several launches over rays. A specular rejection loop that
+ * hits its bound is reported as by pt_ctx_render (PT_E_RUNAWAY, the results are still written).
+ * Synchronous, and leaves a progressive sum as it is. */
+int pt_ctx_trace(pt_ctx* ctx, const float* origins, const float* dirs, int64_t n,
+                 const pt_trace_params* params, float* rgb_out, int is_device, pt_trace_stats* stats);
 
 /* Number of rows of part `part_index` for the given partition. */
 int32_t pt_part_rows(int32_t res_y, int32_t part_index, int32_t part_count, int32_t band_rows);

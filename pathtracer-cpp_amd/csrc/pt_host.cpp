@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <array>
 #include <atomic>
+#include <chrono>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -1038,6 +1039,35 @@ int pt_scene_info(const pt_scene* scene, int32_t* info, int32_t n) {
 // BVH::intersect (bvh.h:156-183) over the caller's own arrays, one ray after the other: the
 // explicit LIFO of node indices (left pushed, then right, so right is popped first), the slab
 // test with inv = 1 / d, a leaf's triangles in tri_idx order, strict t_ < t.
+static int32_t walk_ray(const pt_scene* scene, std::vector<int32_t>& stack, v3 o, v3 d, float& t_out) {
+    const v3 inv{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
+    int32_t ret = -1;
+    float t = 1e30f;
+    stack.assign(1, 0);
+    while (!stack.empty()) {
+        const pt_bvh_node& cur = scene->nodes[stack.back()];
+        stack.pop_back();
+        if (!slab_hit(v3{cur.lb[0], cur.lb[1], cur.lb[2]}, v3{cur.rt[0], cur.rt[1], cur.rt[2]}, o, inv)) continue;
+        if (cur.left == -1 && cur.right == -1) {
+            for (int i = cur.tri_start; i <= cur.tri_end; i++) {
+                const int32_t ti = scene->tri_idx[i];
+                const float* v = scene->verts + 9 * (size_t)ti;
+                const v3 v1{v[0], v[1], v[2]};
+                float t_;
+                if (tri_hit(v1, sub(v3{v[3], v[4], v[5]}, v1), sub(v3{v[6], v[7], v[8]}, v1), o, d, t_) && t_ < t) {
+                    t = t_;
+                    ret = ti;
+                }
+            }
+        } else {
+            stack.push_back(cur.left);
+            stack.push_back(cur.right);
+        }
+    }
+    t_out = t;
+    return ret;
+}
+
 int pt_bvh_intersect(const pt_scene* scene, const float* origins, const float* dirs, int64_t n, float* t_out,
                      int32_t* tri_out) {
     if (n < 0) return set_error(PT_E_ARG, "pt_bvh_intersect: n = %lld is negative", (long long)n);
@@ -1051,34 +1081,99 @@ int pt_bvh_intersect(const pt_scene* scene, const float* origins, const float* d
     for (int64_t r = 0; r < n; r++) {
         const float* po = origins + 3 * r;
         const float* pd = dirs + 3 * r;
-        const v3 o{po[0], po[1], po[2]}, d{pd[0], pd[1], pd[2]};
-        const v3 inv{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
-        int32_t ret = -1;
-        float t = 1e30f;
-        stack.assign(1, 0);
-        while (!stack.empty()) {
-            const pt_bvh_node& cur = scene->nodes[stack.back()];
-            stack.pop_back();
-            if (!slab_hit(v3{cur.lb[0], cur.lb[1], cur.lb[2]}, v3{cur.rt[0], cur.rt[1], cur.rt[2]}, o, inv)) continue;
-            if (cur.left == -1 && cur.right == -1) {
-                for (int i = cur.tri_start; i <= cur.tri_end; i++) {
-                    const int32_t ti = scene->tri_idx[i];
-                    const float* v = scene->verts + 9 * (size_t)ti;
-                    const v3 v1{v[0], v[1], v[2]};
-                    float t_;
-                    if (tri_hit(v1, sub(v3{v[3], v[4], v[5]}, v1), sub(v3{v[6], v[7], v[8]}, v1), o, d, t_) && t_ < t) {
-                        t = t_;
-                        ret = ti;
-                    }
-                }
-            } else {
-                stack.push_back(cur.left);
-                stack.push_back(cur.right);
-            }
-        }
-        t_out[r] = t;
-        tri_out[r] = ret;
+        tri_out[r] = walk_ray(scene, stack, v3{po[0], po[1], po[2]}, v3{pd[0], pd[1], pd[2]}, t_out[r]);
     }
+    return PT_OK;
+}
+
+// trace() (render.h:36-61) for a batch of the caller's rays on the host, with the arithmetic of
+// the device path (pt_paths.hip: shade and finish_path of pt_trace.h): the walk above, the
+// packed normal normalize(cross(e1, e2)) faced as Triangle::normal, the samplers of pt_math.h,
+// the recursion unwound from (triangle, cosine) records, and the per-ray sum in sample order.
+int pt_bvh_trace(const pt_scene* scene, const float* origins, const float* dirs, int64_t n, const pt_trace_params* prm,
+                 float* rgb_out, pt_trace_stats* stats) {
+    const auto t_start = std::chrono::steady_clock::now();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!prm) return set_error(PT_E_ARG, "pt_bvh_trace: params is NULL");
+    if (n < 0) return set_error(PT_E_ARG, "pt_bvh_trace: n = %lld is negative", (long long)n);
+    if (prm->depth < 0 || prm->depth > PT_MAX_DEPTH)
+        return set_error(PT_E_ARG, "pt_bvh_trace: depth %d outside 0..%d", prm->depth, PT_MAX_DEPTH);
+    if (prm->spp < 1 || prm->spp > kTraceMaxSpp)
+        return set_error(PT_E_ARG, "pt_bvh_trace: spp %d outside 1..%d", prm->spp, kTraceMaxSpp);
+    PackedScene ps;
+    const int rc = pack_scene(scene, ps);  // pt_scene_validate's checks: the walk cannot leave the arrays
+    if (rc) return rc;
+    if (n == 0) return PT_OK;
+    if (!origins || !dirs || !rgb_out) return set_error(PT_E_ARG, "pt_bvh_trace: NULL argument");
+    std::vector<int32_t> stack;
+    stack.reserve((size_t)ps.stack_size + 1);
+    const int depth = prm->depth, spp = prm->spp;
+    int32_t rec_tri[PT_MAX_DEPTH];
+    float rec_cos[PT_MAX_DEPTH];
+    uint64_t rays = 0, runaway = 0;
+    for (int64_t r = 0; r < n; r++) {
+        float sum[3] = {0.0f, 0.0f, 0.0f};
+        for (int s = 0; s < spp; s++) {
+            Lcg g{prm->states ? prm->states[(size_t)r * spp + s] : pt_sample_seed((uint32_t)r, (uint32_t)s, prm->seed)};
+            v3 o{origins[3 * r], origins[3 * r + 1], origins[3 * r + 2]};
+            v3 d{dirs[3 * r], dirs[3 * r + 1], dirs[3 * r + 2]};
+            v3 L{0.0f, 0.0f, 0.0f};
+            int k = 0;
+            while (k < depth) {  // depth == 0: trace() returns 0 (render.h:37)
+                float t;
+                rays++;
+                const int32_t ti = walk_ray(scene, stack, o, d, t);
+                if (ti < 0) break;  // miss -> 0
+                const pt_material& m = scene->materials[ti];
+                if (m.type == PT_MAT_EMIT) {
+                    L = v3{m.emit[0], m.emit[1], m.emit[2]};
+                    break;
+                }
+                if (k + 1 >= depth) {  // trace(0) returns 0: emission + ((2 * 0) * albedo) * cos, no draw needed
+                    L = v3{m.emit[0] + 0.0f * m.color[0], m.emit[1] + 0.0f * m.color[1], m.emit[2] + 0.0f * m.color[2]};
+                    break;
+                }
+                const float* v = scene->verts + 9 * (size_t)ti;
+                const v3 v1{v[0], v[1], v[2]};
+                v3 nrm = normalize(cross(sub(v3{v[3], v[4], v[5]}, v1), sub(v3{v[6], v[7], v[8]}, v1)));
+                if (!(dot(nrm, d) < 0.0f)) nrm = neg(nrm);  // triangle.h:48
+                const v3 hp = add(o, scale(d, t));
+                v3 nd;
+                if (m.type == PT_MAT_SPECULAR) {
+                    if (!specular_dir(g, d, nrm, m.roughness, kSpecularIterBound, nd)) runaway++;
+                } else {
+                    nd = hemisphere_dir(g, nrm);
+                }
+                rec_tri[k] = ti;
+                rec_cos[k] = dot(nrm, nd);
+                o = add(hp, scale(nrm, 1e-4f));  // SHIFT_BIAS, render.h:16, 52
+                d = nd;
+                k++;
+            }
+            for (int j = k - 1; j >= 0; j--) {  // render.h:60
+                const pt_material& m = scene->materials[rec_tri[j]];
+                const float c = rec_cos[j];
+                L = v3{m.emit[0] + ((2.0f * L.x) * m.color[0]) * c, m.emit[1] + ((2.0f * L.y) * m.color[1]) * c,
+                       m.emit[2] + ((2.0f * L.z) * m.color[2]) * c};
+            }
+            sum[0] = sum[0] + L.x;  // image.h:27-31
+            sum[1] = sum[1] + L.y;
+            sum[2] = sum[2] + L.z;
+        }
+        const float fs = (float)spp;
+        rgb_out[3 * r] = sum[0] / fs;  // image.h:37-40
+        rgb_out[3 * r + 1] = sum[1] / fs;
+        rgb_out[3 * r + 2] = sum[2] / fs;
+    }
+    if (stats) {
+        stats->rays = rays;
+        stats->paths = (uint64_t)n * (uint64_t)spp;
+        stats->runaway = runaway;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    }
+    if (runaway != 0)
+        return set_error(PT_E_RUNAWAY, "%llu specular rejection loops hit the %d-iteration bound",
+                         (unsigned long long)runaway, kSpecularIterBound);
     return PT_OK;
 }
 

@@ -86,6 +86,11 @@ static_assert(kMaxLdsMaterials <= kMaxLdsRowsByte, "LDS material rows must fit t
 // (lds_usable_per_cu, pt_kernel.hip).
 constexpr size_t kLdsUsable = 161280;
 constexpr size_t kLdsGranule = 256;
+// trace() on caller-supplied rays (pt_bvh_trace, pt_ctx_trace): the bound on material.h:20-23's
+// rejection loop (kMaxSpecularIters of the kernels) and the most samples per ray, so that one
+// ray's records always fit a launch (pt_ctx_trace cuts launches over rays only).
+constexpr int kSpecularIterBound = 1 << 16;
+constexpr int kTraceMaxSpp = 1 << 20;
 constexpr int kPairQueueMin = 256;  // shortest flat pair queue (entries per wave) the launch picks for occupancy
 
 struct PackedScene {
@@ -153,5 +158,34 @@ int query_launch(void* stream, const QueryScene& sc, const QueryPlan& plan, int 
 int aov_launch(void* stream, const QueryScene& sc, const QueryPlan& plan, const pt_camera* cam, const pt_params* prm,
                int32_t rows, int32_t sample, const pt_aov* out, int* gstack, unsigned long long* hits,
                int force_exact);
+
+// ---- trace() on caller-supplied rays (pt_paths.hip; the entry point is in pt_kernel.hip) ----
+// Where a launch keeps the scene, the walk's stack and the path records, and its grid (paths_plan).
+struct PathsPlan {
+    int lds_scene, lds_stack, lds_rec;  // 1: in LDS; 0: read through L1/L2 / rows in a global buffer
+    int rows;                           // stack rows per lane = max(1, tree depth)
+    int rec;                            // path records per lane = depth - 1
+    int grid;                           // blocks of kBlock lanes
+    size_t lds_bytes;                   // dynamic LDS per block
+    size_t stack_ints;                  // ints the global stack buffer must hold (0 with the stack in LDS)
+    size_t rec_words;                   // 32-bit words EACH of the two global record arrays must hold
+};
+// `items`: rays x samples of the largest launch; depth >= 1.
+int paths_plan(const QueryScene& sc, size_t lds_usable, int num_cus, int depth, int64_t items, PathsPlan& plan);
+// One launch over m rays x spp samples (device pointers; m * spp < 2^31); no synchronisation.
+struct PathsLaunch {
+    const float* org;         // m x 3
+    const float* dir;         // m x 3
+    const uint32_t* states;   // m x spp, or nullptr: pt_sample_seed(ray_base + i, s, seed)
+    int32_t m, spp, depth;
+    uint32_t seed, ray_base;
+    float* slab;              // m * spp records of 3 floats, [sample][ray][rgb]
+    unsigned long long* ctr;  // zeroed 4 x u64 (work head at [0]); ray count added at [1], runaway at [3]
+    int* gstack;              // plan.stack_ints ints
+    float* grec;              // 2 * plan.rec_words words: material rows, then cosines
+    const void* theta_tab;    // the device's theta table (float2), or nullptr
+    int theta_lanes, dark, force_exact;
+};
+int paths_launch(void* stream, const QueryScene& sc, const PathsPlan& plan, const PathsLaunch& l);
 
 }  // namespace pt

@@ -322,6 +322,16 @@ struct pt_ctx {
     float* d_qbuf = nullptr;                 // staging of a host-pointer call's rays / channels and results
     size_t qbuf_floats = 0;
     unsigned long long* d_qhits = nullptr;   // hit counter of a call
+    // trace() on caller-supplied rays (pt_ctx_trace): buffers of its own, so a progressive sum stays valid
+    float* d_tslab = nullptr;                // dense radiance slab of one launch, [sample][ray][rgb]
+    size_t tslab_floats = 0;
+    float* d_trec = nullptr;                 // path records, when they do not go to LDS
+    size_t trec_words = 0;
+    float* d_tbuf = nullptr;                 // staging of a host-pointer call's rays and results
+    size_t tbuf_floats = 0;
+    float* d_tstates = nullptr;              // staging of a host-pointer call's LCG states (uint32)
+    size_t tstates_words = 0;
+    unsigned long long* d_tctr = nullptr;    // work head, ray and runaway counters of a call (4 x u64)
     // progressive rendering: d_accum holds the running sum of prog_spp samples
     bool prog_valid = false;
     int prog_spp = 0;
@@ -1439,7 +1449,8 @@ void pt_ctx_destroy(pt_ctx* c) {
     if (last) theta_table_release(c->device);  // no context left on the device to read it (re-checked there)
     for (void* p : {(void*)c->d_nodes, (void*)c->d_tris, (void*)c->d_mats, (void*)c->d_leaves, (void*)c->d_wide, (void*)c->d_wtris, (void*)c->d_nrm, (void*)c->d_umats, (void*)c->d_radiance, (void*)c->d_flags,
                     (void*)c->d_accum, (void*)c->d_out, (void*)c->d_ctr, (void*)c->d_stamps, (void*)c->d_rgb8, (void*)c->d_thr, (void*)c->d_xstack,
-                    (void*)c->d_rank_tri, (void*)c->d_qstack, (void*)c->d_qbuf, (void*)c->d_qhits})
+                    (void*)c->d_rank_tri, (void*)c->d_qstack, (void*)c->d_qbuf, (void*)c->d_qhits,
+                    (void*)c->d_tslab, (void*)c->d_trec, (void*)c->d_tbuf, (void*)c->d_tstates, (void*)c->d_tctr})
         if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -2410,6 +2421,164 @@ int pt_ctx_render_aov(pt_ctx* c, const pt_camera* cam, const pt_params* prm, int
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
     return query_finish(c, plan, (uint64_t)npix, ms, 1, t_start, stats);
+}
+
+// trace() (render.h:36-61) along the caller's rays: pt_paths_kernel fills a dense slab
+// [sample][ray][rgb] of one launch, pt_accumulate_kernel adds a ray's samples in order and
+// divides. Launches are cut over rays only: m rays with m * spp < 2^31 records inside the slab
+// budget (PT_TRACE_CHUNK, test hook: rays per launch).
+int pt_ctx_trace(pt_ctx* c, const float* origins, const float* dirs, int64_t n, const pt_trace_params* prm,
+                 float* rgb_out, int is_device, pt_trace_stats* stats) {
+    const auto t_start = std::chrono::steady_clock::now();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!c) return set_error(PT_E_ARG, "pt_ctx_trace: context is NULL");
+    if (!prm) return set_error(PT_E_ARG, "pt_ctx_trace: params is NULL");
+    if (n < 0) return set_error(PT_E_ARG, "pt_ctx_trace: n = %lld is negative", (long long)n);
+    if (prm->depth < 0 || prm->depth > PT_MAX_DEPTH)
+        return set_error(PT_E_ARG, "pt_ctx_trace: depth %d outside 0..%d", prm->depth, PT_MAX_DEPTH);
+    if (prm->spp < 1 || prm->spp > kTraceMaxSpp)
+        return set_error(PT_E_ARG, "pt_ctx_trace: spp %d outside 1..%d", prm->spp, kTraceMaxSpp);
+    if (!c->have_scene) return set_error(PT_E_ARG, "pt_ctx_trace: no scene set");
+    if (n == 0) return PT_OK;
+    if (!origins || !dirs || !rgb_out) return set_error(PT_E_ARG, "pt_ctx_trace: NULL argument");
+    if (int rc0 = ctx_ready(c)) return rc0;
+    HIP_TRY(hipSetDevice(c->device));
+    const int64_t spp = prm->spp;
+    auto finish = [&](const PathsPlan* plan, const unsigned long long* ctr, double kms, double rms, int launches) {
+        if (!stats) return;
+        stats->rays = ctr[1];
+        stats->paths = (uint64_t)n * (uint64_t)spp;
+        stats->runaway = ctr[3];
+        stats->kernel_ms = kms;
+        stats->reduce_ms = rms;
+        stats->launches = launches;
+        if (plan) {
+            stats->lds_scene = plan->lds_scene;
+            stats->lds_stack = plan->lds_stack;
+            stats->lds_records = plan->lds_rec;
+        }
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    };
+    if (prm->depth == 0) {  // trace() returns 0 (render.h:37): no ray is traced
+        if (is_device) {
+            HIP_TRY(hipMemsetAsync(rgb_out, 0, 3 * sizeof(float) * (size_t)n, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+        } else {
+            memset(rgb_out, 0, 3 * sizeof(float) * (size_t)n);
+        }
+        const unsigned long long zero[4] = {0, 0, 0, 0};
+        finish(nullptr, zero, 0, 0, 0);
+        return PT_OK;
+    }
+    // rays per launch
+    int64_t m_max = std::min<int64_t>(n, ((1ll << 31) - 1) / spp);
+    m_max = std::min<int64_t>(m_max, (int64_t)(batch_bytes_budget(c->device, false) / (3 * sizeof(float) * (size_t)spp)));
+    if (!is_device) m_max = std::min(m_max, kQueryHostChunk);
+    if (const char* tc = hook_env("PT_TRACE_CHUNK"))
+        if (*tc) m_max = std::min<int64_t>(m_max, strtoll(tc, nullptr, 10));
+    m_max = std::max<int64_t>(m_max, 1);
+    const QueryScene sc = query_scene(c);
+    PathsPlan plan;
+    int rc;
+    if ((rc = paths_plan(sc, c->lds_usable, c->num_cus, prm->depth, m_max * spp, plan))) return rc;
+    if (plan.stack_ints > c->qstack_ints) {
+        if (c->d_qstack) (void)hipFree(c->d_qstack);
+        c->d_qstack = nullptr;
+        c->qstack_ints = 0;
+        HIP_TRY(hipMalloc((void**)&c->d_qstack, plan.stack_ints * sizeof(int)));
+        c->qstack_ints = plan.stack_ints;
+    }
+    if (plan.rec_words > 0 && (rc = ensure(&c->d_trec, &c->trec_words, 2 * plan.rec_words))) return rc;
+    if ((rc = ensure(&c->d_tslab, &c->tslab_floats, 3 * (size_t)(m_max * spp)))) return rc;
+    if (!c->d_tctr) HIP_TRY(hipMalloc((void**)&c->d_tctr, 4 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(c->d_tctr, 0, 4 * sizeof(unsigned long long), c->stream));
+    // host pointers: staging [origins 3][dirs 3][rgb 3] x m_max, and the states
+    float *s_org = nullptr, *s_dir = nullptr, *s_out = nullptr;
+    if (!is_device) {
+        if ((rc = ensure(&c->d_tbuf, &c->tbuf_floats, 9 * (size_t)m_max))) return rc;
+        s_org = c->d_tbuf;
+        s_dir = s_org + 3 * m_max;
+        s_out = s_dir + 3 * m_max;
+        if (prm->states && (rc = ensure(&c->d_tstates, &c->tstates_words, (size_t)(m_max * spp)))) return rc;
+    }
+    PathsLaunch l{};
+    l.spp = (int32_t)spp;
+    l.depth = prm->depth;
+    l.seed = prm->seed;
+    l.slab = c->d_tslab;
+    l.ctr = c->d_tctr;
+    l.gstack = c->d_qstack;
+    l.grec = plan.rec_words > 0 ? c->d_trec : nullptr;
+    l.dark = c->dark ? 1 : 0;
+    l.force_exact = query_force_exact();
+#if PT_THETA_TAB
+    {
+        // as pt_ctx_render: the theta table only for scenes with a SPECULAR material
+        const char* tl = hook_env("PT_THETA_LANES");
+        l.theta_lanes = (tl && *tl) ? atoi(tl) : (c->has_specular ? 32 : 0);
+        if (PT_THETA_TAB == 1 || l.theta_lanes > 0) {
+            const float2* tab = nullptr;
+            if ((rc = theta_table(c, &tab))) {
+                if (PT_THETA_TAB == 1) return rc;
+                tab = nullptr;  // the computed hemisphere_dir gives the same bits
+            }
+            l.theta_tab = tab;
+        }
+    }
+#endif
+    EventPair ev, ev2;
+    HIP_TRY(hipEventCreate(&ev.a));
+    HIP_TRY(hipEventCreate(&ev.b));
+    HIP_TRY(hipEventCreate(&ev2.a));
+    double kernel_ms = 0, reduce_ms = 0;
+    int launches = 0;
+    for (int64_t i0 = 0; i0 < n; i0 += m_max) {
+        const int32_t m = (int32_t)std::min(m_max, n - i0);
+        l.m = m;
+        l.ray_base = (uint32_t)i0;
+        l.org = origins + 3 * i0;
+        l.dir = dirs + 3 * i0;
+        l.states = prm->states ? prm->states + i0 * spp : nullptr;
+        float* k_out = rgb_out + 3 * i0;
+        if (!is_device) {
+            HIP_TRY(hipMemcpyAsync(s_org, l.org, 3 * sizeof(float) * (size_t)m, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(s_dir, l.dir, 3 * sizeof(float) * (size_t)m, hipMemcpyHostToDevice, c->stream));
+            if (prm->states) {
+                HIP_TRY(hipMemcpyAsync(c->d_tstates, l.states, sizeof(uint32_t) * (size_t)(m * spp), hipMemcpyHostToDevice,
+                                       c->stream));
+                l.states = reinterpret_cast<const uint32_t*>(c->d_tstates);
+            }
+            l.org = s_org;
+            l.dir = s_dir;
+            k_out = s_out;
+        }
+        HIP_TRY(hipMemsetAsync(c->d_tctr, 0, sizeof(unsigned long long), c->stream));  // work head only
+        HIP_TRY(hipEventRecord(ev.a, c->stream));
+        if ((rc = paths_launch(c->stream, sc, plan, l))) return rc;
+        HIP_TRY(hipEventRecord(ev.b, c->stream));
+        // the ray's samples in order from +0, then / spp (image.h:27-31, 37-40)
+        hipLaunchKernelGGL(pt_accumulate_kernel, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->d_tslab,
+                           (float*)nullptr, k_out, (int)m, (int)spp, 1, 1, 0, (float)spp, (const uint32_t*)nullptr, 0);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(ev2.a, c->stream));
+        launches++;
+        if (!is_device)
+            HIP_TRY(hipMemcpyAsync(rgb_out + 3 * i0, s_out, 3 * sizeof(float) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
+        kernel_ms += ms;
+        HIP_TRY(hipEventElapsedTime(&ms, ev.b, ev2.a));
+        reduce_ms += ms;
+    }
+    unsigned long long h_ctr[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h_ctr, c->d_tctr, sizeof(h_ctr), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    finish(&plan, h_ctr, kernel_ms, reduce_ms, launches);
+    if (h_ctr[3] != 0)
+        return set_error(PT_E_RUNAWAY, "%llu specular rejection loops hit the %d-iteration bound", h_ctr[3],
+                         kMaxSpecularIters);
+    return PT_OK;
 }
 
 }  // extern "C"

@@ -28,18 +28,12 @@
 #include <algorithm>
 
 #include "pt_internal.h"
+#include "pt_raygate.h"
 #include "pt_trace.h"
 
 namespace pt {
 
 FastDiv fastdiv_for(uint32_t d);  // make_fastdiv (pt_kernel.hip)
-
-// The slab test's IEEE min/max form (slab_hit_finite) holds for rays inside bounded_ray's
-// domain. v_max_f32 drops a NaN operand, so a ray with one NaN component could pass
-// bounded_ray's maxima; a caller's ray is checked for NaN separately (fabs(NaN) < inf is false).
-__device__ __forceinline__ bool query_ray_bounded(v3 o, v3 inv) {
-    return bounded_ray(o, inv) && all_finite(o) && all_finite(inv);
-}
 
 // intersect_tree's walk, stopping at the first triangle hit with t < tmax (see above).
 template <bool kFiniteInv, typename NodePtr, typename TriPtr>

@@ -5,7 +5,8 @@
 // libpt_hip.so, which runs the per-pixel trace loop on every visible GPU, gathers the
 // row bands on the first one and applies gamma_correct(2.2) + save_png's quantisation
 // there (pt_render_rgb8_devices): the host receives the PNG's bytes (3 B per pixel
-// instead of 12) and writes them. The per-row (render.h:87) / per-chunk (render.h:136)
+// instead of 12) and writes them. trace (render.h:36-61) keeps its signature and runs on the
+// host, one ray at a time; BVH::trace_batch (pt_scene.hpp) is its batched form on the GPU. The per-row (render.h:87) / per-chunk (render.h:136)
 // progress lines follow the library's progress reports. The OpenGL tile path and the
 // SFML viewer (render_realtime) are not part of this framework.
 #pragma once
@@ -38,6 +39,24 @@ struct Timer {
         return ms.count() / 1000.0f;
     }
 };
+
+// trace (render.h:36-61), on the host: the radiance arriving along one ray, `depth` segments at
+// most. It draws from the global `rng`, which continues from call to call, as the reference's does.
+// For many rays use BVH::trace_batch (the GPU when one is visible, per-ray streams).
+inline vec3 trace(const BVH& bvh, const vec3& ray_o, const vec3& ray_d, int depth) {
+    if (depth == 0) return 0;
+    float t;
+    const int idx = bvh.intersect(ray_o, ray_d, t);
+    if (idx == -1) return 0;
+    const Triangle& tri = bvh.triangles[idx];
+    const Material& mat = tri.material;
+    if (mat.type == Material::EMIT) return mat.emit_color;
+    const vec3 p = ray_o + ray_d * t;
+    const vec3 n = tri.normal(ray_d, p);
+    const vec3 next_d = mat.reflected_dir(ray_d, n);  // drawn before the recursion, as render.h:51
+    const vec3 incoming = trace(bvh, p + n * SHIFT_BIAS, next_d, depth - 1);
+    return mat.emit_color + 2 * incoming * mat.color * n.dot(next_d);  // the cosine weight's factor 2, render.h:60
+}
 
 inline int ceildiv(int a, int b) { return (a + b - 1) / b; }
 

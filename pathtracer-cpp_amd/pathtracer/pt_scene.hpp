@@ -232,6 +232,32 @@ struct BVH {
         if (rc != PT_OK) throw std::runtime_error(std::string("BVH::intersect_batch: ") + pt_last_error());
     }
 
+    // Extension: trace() (render.h:36-61) for n rays (o, d: n x 3 floats; rgb: n x 3 results), `samples`
+    // paths per ray summed in order and divided by `samples`. Sample s of ray i starts the LCG at
+    // pt_sample_seed(i, s, seed); the global `rng` is not touched. On HIP device `device` when one is
+    // visible (pt_ctx_trace), otherwise the same arithmetic on the host (pt_bvh_trace): the same bits
+    // either way. The BVH must be built. Throws on failure.
+    void trace_batch(const float* o, const float* d, size_t n, int depth, int samples, unsigned seed, float* rgb,
+                     int device = 0) const {
+        if (!built) throw std::runtime_error("BVH::trace_batch: BVH not built");
+        const std::vector<float> v = packed_vertices();
+        const std::vector<pt_material> m = packed_materials();
+        const pt_scene sc{(int32_t)triangles.size(), v.data(), m.data(), (int32_t)nodes.size(),
+                          reinterpret_cast<const pt_bvh_node*>(nodes.data()), tri_idx.data()};
+        const pt_trace_params prm{depth, samples, seed, nullptr};
+        int rc;
+        if (pt_device_count() > 0) {
+            pt_ctx* ctx = nullptr;
+            rc = pt_ctx_create(device, &ctx);
+            if (rc == PT_OK) rc = pt_ctx_set_scene(ctx, &sc);
+            if (rc == PT_OK) rc = pt_ctx_trace(ctx, o, d, (int64_t)n, &prm, rgb, 0, nullptr);
+            pt_ctx_destroy(ctx);
+        } else {
+            rc = pt_bvh_trace(&sc, o, d, (int64_t)n, &prm, rgb, nullptr);
+        }
+        if (rc != PT_OK) throw std::runtime_error(std::string("BVH::trace_batch: ") + pt_last_error());
+    }
+
     // Wavefront OBJ + MTL import with the reference's material mapping (bvh.h:184-242):
     // illum 1 -> DIFFUSE(Kd), illum 2 -> EMIT(Ka), otherwise DIFFUSE(0.5). Polygons are
     // fan-triangulated; faces must reference a material (the reference indexes

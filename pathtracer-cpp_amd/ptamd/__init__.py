@@ -79,6 +79,15 @@ def _rays(origins, directions) -> Tuple[np.ndarray, np.ndarray]:
     return o, d
 
 
+def _states(states, n: int, samples: int) -> Optional[np.ndarray]:
+    if states is None:
+        return None
+    st = np.ascontiguousarray(states, dtype=np.uint32).reshape(-1)
+    if st.shape[0] != n * samples:
+        raise ValueError("states must hold n x samples uint32 values")
+    return st
+
+
 def _is_tensor(x) -> bool:
     return hasattr(x, "data_ptr")
 
@@ -235,6 +244,23 @@ class BVH:
         check(lib().pt_bvh_intersect(C.byref(ref.s), o.ctypes.data, d.ctypes.data, o.shape[0], t.ctypes.data,
                                      tri.ctypes.data))
         return t, tri
+
+    def trace(self, origins, directions, depth: int, samples: int = 1, seed: int = PT_SEED, states=None):
+        """trace() (render.h:36-61) along a batch of rays on the host (pt_bvh_trace; no device
+        needed), bit-identical to Renderer.trace: origins and directions (n, 3) float32 ->
+        (rgb (n, 3) float32, stats). rgb[i] is the float32 sum of `samples` paths of ray i in
+        order, divided by `samples`; sample s of ray i starts the LCG at states[i, s] (uint32,
+        (n, samples)) or, with states None, at pt_sample_seed(i, s, seed)."""
+        ref = _SceneRef(self)
+        o, d = _rays(origins, directions)
+        n = o.shape[0]
+        st_arr = _states(states, n, samples)
+        prm = _lib.pt_trace_params(depth, samples, seed, st_arr.ctypes.data if st_arr is not None else None)
+        rgb = np.empty((n, 3), dtype=np.float32)
+        st = _lib.pt_trace_stats()
+        check(lib().pt_bvh_trace(C.byref(ref.s), o.ctypes.data, d.ctypes.data, n, C.byref(prm), rgb.ctypes.data,
+                                 C.byref(st)))
+        return rgb, st.as_dict()
 
     @classmethod
     def from_scene(cls, scene) -> "BVH":
@@ -433,6 +459,39 @@ class Renderer:
                                      tm.ctypes.data if tm is not None else None,
                                      None if any_hit else t.ctypes.data, res.ctypes.data, 0, C.byref(st)))
         return (res if any_hit else (t, res)), st.as_dict()
+
+    def trace(self, origins, directions, depth: int, samples: int = 1, seed: int = PT_SEED, states=None, out=None):
+        """Radiance along a batch of the caller's rays on this context's scene (pt_ctx_trace;
+        every path is trace()'s, render.h:36-61): (rgb (n, 3) float32, stats). rgb[i] is the
+        float32 sum of `samples` paths of ray i in order, divided by `samples`; sample s of ray i
+        starts the LCG at states[i, s] (uint32, n x samples) or, with states None, at
+        pt_sample_seed(i, s, seed). numpy arrays go through host pointers. Contiguous torch
+        tensors on this context's device (float32 rays, `states` of a 32-bit integer type) go
+        through the device-pointer path: `out`, a float32 tensor of n x 3 elements, is written
+        in place and returned, and the inputs are left untouched."""
+        st = _lib.pt_trace_stats()
+        if _is_tensor(origins):
+            n = origins.numel() // 3
+            if out is None:
+                import torch
+                out = torch.empty((n, 3), dtype=torch.float32, device=origins.device)
+            tens = [origins, directions, out] + ([states] if states is not None else [])
+            for x in tens:
+                if not x.is_contiguous() or not x.is_cuda or x.element_size() != 4:
+                    raise ValueError("tensors must be contiguous 32-bit tensors on the context's device")
+            if directions.numel() != 3 * n or out.numel() != 3 * n or (states is not None and states.numel() != n * samples):
+                raise ValueError("directions and out must hold n x 3 elements, states n x samples")
+            prm = _lib.pt_trace_params(depth, samples, seed, states.data_ptr() if states is not None else None)
+            check(lib().pt_ctx_trace(self.h, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()), n,
+                                     C.byref(prm), C.c_void_p(out.data_ptr()), 1, C.byref(st)))
+            return out, st.as_dict()
+        o, d = _rays(origins, directions)
+        n = o.shape[0]
+        st_arr = _states(states, n, samples)
+        prm = _lib.pt_trace_params(depth, samples, seed, st_arr.ctypes.data if st_arr is not None else None)
+        rgb = np.empty((n, 3), dtype=np.float32)
+        check(lib().pt_ctx_trace(self.h, o.ctypes.data, d.ctypes.data, n, C.byref(prm), rgb.ctypes.data, 0, C.byref(st)))
+        return rgb, st.as_dict()
 
     def aov(self, camera: Camera, sample: int = 0, seed: int = PT_SEED,
             channels: Sequence[str] = _lib.pt_aov.CHANNELS, part_index: int = 0, part_count: int = 1,

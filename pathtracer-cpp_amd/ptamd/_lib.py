@@ -29,6 +29,7 @@ EXPORTED = (
     "pt_debug_rccl_failover", "pt_debug_rtc_cache", "pt_devices_release", "pt_debug_ctx_flags", "pt_debug_counter",
     "pt_debug_scene_dark", "pt_debug_rtc_start", "pt_debug_pack_hash",
     "pt_bvh_intersect", "pt_ctx_intersect", "pt_ctx_render_aov",
+    "pt_bvh_trace", "pt_ctx_trace",
 )
 PT_MAX_DEVICES = 16
 
@@ -92,6 +93,20 @@ class pt_query_stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class pt_trace_params(C.Structure):
+    """trace() on caller-supplied rays (include/pt_hip.h); states NULL = pt_sample_seed(i, s, seed)."""
+    _fields_ = [("depth", C.c_int32), ("spp", C.c_int32), ("seed", C.c_uint32), ("states", C.c_void_p)]
+
+
+class pt_trace_stats(C.Structure):
+    _fields_ = [("rays", C.c_uint64), ("paths", C.c_uint64), ("runaway", C.c_uint64), ("kernel_ms", C.c_double),
+                ("reduce_ms", C.c_double), ("total_ms", C.c_double), ("launches", C.c_int32),
+                ("lds_scene", C.c_int32), ("lds_stack", C.c_int32), ("lds_records", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class pt_aov(C.Structure):
     """First-hit channels (include/pt_hip.h); a NULL pointer skips the channel."""
     CHANNELS = ("t", "tri", "normal", "albedo", "emission", "ray")
@@ -99,7 +114,7 @@ class pt_aov(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in CHANNELS]
 
 
-assert C.sizeof(pt_bvh_node) == 40 and C.sizeof(pt_material) == 32
+assert C.sizeof(pt_bvh_node) == 40 and C.sizeof(pt_material) == 32 and C.sizeof(pt_trace_stats) == 64
 
 
 class PTError(RuntimeError):
@@ -189,6 +204,9 @@ def lib() -> C.CDLL:
         L.pt_ctx_intersect.argtypes = [P, P, P, C.c_int64, C.c_int, P, P, P, C.c_int, C.POINTER(pt_query_stats)]
         L.pt_ctx_render_aov.argtypes = [P, C.POINTER(pt_camera), C.POINTER(pt_params), C.c_int32, C.POINTER(pt_aov),
                                         C.c_int, C.POINTER(pt_query_stats)]
+        L.pt_bvh_trace.argtypes = [C.POINTER(pt_scene), P, P, C.c_int64, C.POINTER(pt_trace_params), P,
+                                   C.POINTER(pt_trace_stats)]
+        L.pt_ctx_trace.argtypes = [P, P, P, C.c_int64, C.POINTER(pt_trace_params), P, C.c_int, C.POINTER(pt_trace_stats)]
         if hasattr(L, "pt_debug_rccl_failover"):  # test hooks (absent from older builds used in A/B runs)
             L.pt_debug_rccl_failover.argtypes = [C.c_int32, C.c_int32, P]
         if hasattr(L, "pt_debug_rtc_cache"):

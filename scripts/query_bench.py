@@ -10,6 +10,16 @@ least --min-ms of HIP-event kernel time; Mray/s = rays / kernel time. Writes
 <out>/<scene>.json (default profiles/query) and prints each file's content as one JSON line.
 
     python3 scripts/query_bench.py [--scenes cornell,sphere223] [--res 1024] [--min-ms 1000]
+
+--mode trace: path-tracing rates of pt_ctx_trace instead. The ray set is the same frame's camera
+rays with the LCG states the render's samples have after their two camera draws (device
+buffers), depth 5, 1 and 16 samples per ray; beside it pt_ctx_render of the same frame and
+samples forced to the binary tree walk (PT_FLAT=0 PT_WIDE=0: the same walk and shading, its own
+camera rays, flagged slab and fused accumulation) and the render on its default kernel. At one
+sample the two images are compared bit for bit before anything is timed (with 16 the render
+jitters a camera ray per sample, the trace repeats sample 0's). Mray/s = traced segments / kernel
+time (trace: the path kernel alone; its in-order sum pass is reported beside it). Writes
+<out>/<scene>.json (default profiles/paths).
 """
 import argparse
 import json
@@ -96,6 +106,92 @@ def bench_scene(name, res, min_ms, warmup, seed):
             "device": torch.cuda.get_device_name(0), "lines": lines}
 
 
+def mix32(x):
+    """pt_mix32 (include/pt_hip.h) on uint32 arrays."""
+    x = x.astype(np.uint32)
+    x ^= x >> np.uint32(16)
+    x *= np.uint32(0x7feb352d)
+    x ^= x >> np.uint32(15)
+    x *= np.uint32(0x846ca68b)
+    x ^= x >> np.uint32(16)
+    return x
+
+
+def camera_states(npix, spp, seed):
+    """(npix, spp) uint32: pt_sample_seed(pixel, s, seed) advanced by the camera's two LCG draws."""
+    with np.errstate(over="ignore"):
+        st = mix32(mix32(np.uint32(seed) * np.ones(1, np.uint32))[0] ^ np.arange(npix, dtype=np.uint32))
+        st = mix32(st[:, None] + np.arange(spp, dtype=np.uint32)[None, :])
+        for _ in range(2):
+            st = st * np.uint32(1664525) + np.uint32(1013904223)
+    return np.ascontiguousarray(st)
+
+
+def bench_trace_scene(name, res, min_ms, warmup, depth=5):
+    import torch
+    import ptamd
+    from ptamd import scenes
+    sc = scenes.cornell((res, res)) if name == "cornell" else scenes.sphere_in_cornell(int(name[len("sphere"):]), (res, res))
+    bvh = ptamd.BVH.from_scene(sc)
+    cam = ptamd.Camera.from_spec(sc.camera)
+    r = ptamd.Renderer(0)
+    r.set_scene(bvh)
+    r.prepare()
+    aov, _ = r.aov(cam, sample=0, channels=("ray",))
+    rays = aov["ray"].reshape(-1, 6)
+    n = rays.shape[0]
+    dev = torch.device("cuda", 0)
+    to = torch.from_numpy(np.ascontiguousarray(rays[:, 0:3])).to(dev)
+    td = torch.from_numpy(np.ascontiguousarray(rays[:, 3:6])).to(dev)
+    out = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    frame = torch.empty(res * res * 3, dtype=torch.float32, device=dev)
+    lines = {}
+    placement = None
+    for spp in (1, 16):
+        states = torch.from_numpy(camera_states(n, spp, ptamd.PT_SEED).view(np.int32)).to(dev)
+        info = {}
+
+        def trace_call():
+            _, st = r.trace(to, td, depth, samples=spp, states=states, out=out)
+            info.update(st)
+            return st["rays"], st["kernel_ms"]
+
+        def render_call(tree):
+            if tree:
+                os.environ["PT_FLAT"], os.environ["PT_WIDE"] = "0", "0"
+            try:
+                _, st = r.render(cam, spp, depth, out=frame)
+            finally:
+                os.environ.pop("PT_FLAT", None)
+                os.environ.pop("PT_WIDE", None)
+            info["kernel"] = ptamd._lib.pt_stats.PATHS.get(st["kernel_path"], str(st["kernel_path"]))
+            info["render_reduce_ms"] = st["reduce_ms"]
+            return st["rays"], st["kernel_ms"]
+
+        # the run checks itself at one sample (the ray set is sample 0's camera rays: with more
+        # samples the render jitters a ray per sample, the trace repeats the one it was given):
+        # same rays, same states, same bits, same segment count
+        t_rays, _ = trace_call()
+        r_rays, _ = render_call(True)
+        if spp == 1:
+            assert t_rays == r_rays and torch.equal(out.reshape(-1).view(torch.int32), frame.view(torch.int32)), \
+                f"{name}: trace and tree-walk render differ"
+        key = f"trace_spp{spp}"
+        lines[key] = timed(trace_call, warmup, min_ms)
+        lines[key].update(sum_pass_ms_per_call=info["reduce_ms"], launches=info["launches"],
+                          call_total_ms=info["total_ms"])
+        placement = {k: info[k] for k in ("lds_scene", "lds_stack", "lds_records")}
+        for tree in (True, False):
+            key = f"render_{'tree' if tree else 'default'}_spp{spp}"
+            lines[key] = timed(lambda: render_call(tree), max(1, warmup // 2), min_ms)
+            lines[key].update(kernel=info["kernel"], sum_pass_ms_per_call=info["render_reduce_ms"])
+        for k in (f"trace_spp{spp}", f"render_default_spp{spp}"):
+            lines[k]["ratio_to_render_tree"] = lines[k]["mrays_per_s"] / lines[f"render_tree_spp{spp}"]["mrays_per_s"]
+    r.close()
+    return {"scene": sc.name, "tris": len(sc.tris), "res": [res, res], "rays": n, "depth": depth, "placement": placement,
+            "min_kernel_ms": min_ms, "device": torch.cuda.get_device_name(0), "lines": lines}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--scenes", default="cornell,sphere223")
@@ -103,11 +199,17 @@ def main():
     ap.add_argument("--min-ms", type=float, default=1000.0, help="kernel time per line")
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "query"))
+    ap.add_argument("--mode", choices=("query", "trace"), default="query")
+    ap.add_argument("--out", default=None, help="default profiles/query, or profiles/paths with --mode trace")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "paths" if args.mode == "trace" else "query")
+    if args.mode == "trace":
+        os.environ["PT_TEST_HOOKS"] = "1"  # PT_FLAT / PT_WIDE pick the yardstick's kernel
     os.makedirs(args.out, exist_ok=True)
     for name in args.scenes.split(","):
-        res = bench_scene(name, args.res, args.min_ms, args.warmup, args.seed)
+        res = bench_trace_scene(name, args.res, args.min_ms, args.warmup) if args.mode == "trace" else \
+            bench_scene(name, args.res, args.min_ms, args.warmup, args.seed)
         with open(os.path.join(args.out, res["scene"] + ".json"), "w") as f:
             json.dump(res, f, indent=1)
             f.write("\n")
