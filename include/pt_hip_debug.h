@@ -58,14 +58,35 @@ int pt_debug_rtc_start(const pt_scene* scene);
 int64_t pt_debug_rtc_cache(int32_t op);
 
 /* Test hook: how a context's scene is rendered. out[0] = 1 if the scene kernel unwinds with
- * pre-doubled albedo (the host's radiance bound passed, pt_kernel.hip: albedo_x2_ok), out[1] =
+ * pre-doubled albedo (the host's radiance bound passed, pt_launch.hip: albedo_x2_ok), out[1] =
  * 1 if the scene holds a SPECULAR material, out[2] = 1 if a hipRTC scene kernel was requested
  * for the scene, out[3] = wide nodes (0 = no wide tree), out[4] = 1 if every bounce material is
  * dark (emission +0, finite albedo: finish_path skips the unwinding of +0 paths). */
 int pt_debug_ctx_flags(const pt_ctx* ctx, int32_t out[5]);
+/* Test hook: the launch plan of ctx's last pt_ctx_render* / pt_ctx_render_progressive call that
+ * reached its launches (all zero before one). out[] in this order:
+ *   [0] kernel_path (PT_PATH_*)   [1] flat   [2] wide   [3] pairs   [4] pair_queue (entries per wave)
+ *   [5] lds_bytes (dynamic LDS per block)   [6] lds_scene
+ *   [7] wide_rows   [8] wide_queue   [9] wide_top   [10] blocks_per_cu (of the last launch)
+ *   [11] batch   [12] per_item   [13] fused   [14] tail
+ *   [15] flags_pm (1 pixel-major bits, 0 sample-major, -1 dense slabs without flag bits)
+ *   [16] trace_launches   [17] regen_thresh   [18] theta_lanes
+ *   of the last launch (0 without one): [19] grid   [20] chunk   [21] static_items
+ *   [22] acc_every (0 when that launch sums no earlier slab)
+ *   [23] the context's num_cus.
+ * [10] and [19..22] depend on the device's CU count, the others on the scene and parameters only. */
+int pt_debug_ctx_plan(const pt_ctx* ctx, int64_t out[24]);
+/* Test hook, no device needed: where the binary walk of the ray queries (tri_f4 = 3 float4 per
+ * triangle in the LDS scene) and of pt_ctx_trace (tri_f4 = 5: with materials) keeps its data for a
+ * tree of num_nodes nodes, num_tris triangles and depth tree_depth, rec_rows path-record rows
+ * (depth - 1) and lds_usable bytes of LDS per CU, under the placement hooks (PT_LDS_SCENE_BYTES,
+ * PT_QUERY_LDS_STACK, PT_TRACE_LDS_REC). out[] = {scene in LDS, stack in LDS, records in LDS,
+ * dynamic LDS bytes per block}. */
+int pt_debug_walk_placement(int32_t num_nodes, int32_t num_tris, int32_t tree_depth, int32_t tri_f4,
+                            int32_t rec_rows, uint64_t lds_usable, int32_t out[4]);
 /* Test hook, no device needed: 1 if `scene` passes the dark-path gate (every non-emitting
  * triangle: emission +0, finite albedo, a unit-length shading normal, SPECULAR roughness
- * |r| <= 1.15 so that cos theta is finite; pt_kernel.hip scene_dark), 0 if not, < 0 on error. */
+ * |r| <= 1.15 so that cos theta is finite; pt_launch.hip scene_dark), 0 if not, < 0 on error. */
 int pt_debug_scene_dark(const pt_scene* scene);
 /* Test hook: process-wide counters. which = 0: contexts created (pt_ctx_create), 1: scene
  * uploads (pt_ctx_set_scene), 2: cached multi-device context sets live, 3: uploads skipped

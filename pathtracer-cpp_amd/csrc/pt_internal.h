@@ -1,4 +1,8 @@
-// pt_internal.h — declarations shared by pt_host.cpp (host C++) and pt_kernel.hip.
+// pt_internal.h — what the translation units of libpt_hip.so share without HIP: errors and
+// hooks, the packed scene (pt_host.cpp builds it, pt_kernel.hip uploads it), a few constants both
+// sides must agree on, and the boundaries between pt_kernel.hip (pt_ctx and its entry points) and
+// pt_multi.hip, pt_query.hip, pt_paths.hip, pt_flat_fast.hip. The launch rules those share are in
+// pt_launch.h, the hipRTC scene kernel in pt_rtc.h; DESIGN.md §3 has the map of the host code.
 #pragma once
 
 #include <stdint.h>
@@ -22,6 +26,13 @@ const char* hook_env(const char* name);
 struct f4 {
     float x, y, z, w;
 };
+
+// Magic numbers of the kernels' division by a launch constant (FastDiv, pt_trace.h; pt_launch.hip).
+struct FastDiv;
+FastDiv make_fastdiv(uint32_t d);
+// pt_launch.h: where the binary walk keeps its data (WalkPlan) and a part's validated shape.
+struct WalkPlan;
+struct PartShape;
 
 // Device layout of a scene (see DESIGN.md "Data layout in HBM"):
 //   nodes: 2 x f4 per node   {lb.xyz, rt.x}, {rt.y, rt.z, a, b}, renumbered so that the two
@@ -83,7 +94,7 @@ static_assert(kMaxLdsMaterials <= kMaxLdsRowsByte, "LDS material rows must fit t
 // rounded to: 6 blocks of 26,816 B run together, 6 of 27,072 B do not (measured on the wide
 // kernel on gfx950 / MI355X, profiles/r03z_lds), although 160 KiB would hold them. Applied
 // only on that architecture, and never above the device's reported LDS per CU
-// (lds_usable_per_cu, pt_kernel.hip).
+// (pt_ctx::lds_usable, set in pt_ctx_create; lds_blocks, pt_launch.h).
 constexpr size_t kLdsUsable = 161280;
 constexpr size_t kLdsGranule = 256;
 // trace() on caller-supplied rays (pt_bvh_trace, pt_ctx_trace): the bound on material.h:20-23's
@@ -138,40 +149,21 @@ struct QueryScene {
     const int32_t* rank_tri;
     int32_t num_nodes, num_tris, tree_depth;
 };
-// Where a launch keeps the walk's stack and the scene, and its grid (query_plan).
-struct QueryPlan {
-    int lds_scene, lds_stack;  // 1: in LDS; 0: read through L1/L2 / rows in the global buffer
-    int rows;                  // stack rows per lane = max(1, tree depth)
-    int grid;                  // blocks of kBlock lanes (grid-stride over the rays or pixels)
-    size_t lds_bytes;          // dynamic LDS per block
-    size_t stack_ints;         // ints the global stack buffer must hold (0 with the stack in LDS)
-};
 // which: 0 closest hit, 1 any hit, 2 AOV. `count`: rays or pixels of the largest launch.
-int query_plan(int which, const QueryScene& sc, size_t lds_usable, int num_cus, int64_t count, QueryPlan& plan);
+int query_plan(int which, const QueryScene& sc, size_t lds_usable, int num_cus, int64_t count, WalkPlan& plan);
 // One launch over n rays (device pointers) on `stream` (a hipStream_t); no synchronisation.
 // `hits` (device): incremented by the number of rays that hit / are occluded.
-int query_launch(void* stream, const QueryScene& sc, const QueryPlan& plan, int any, const float* org, const float* dir,
+int query_launch(void* stream, const QueryScene& sc, const WalkPlan& plan, int any, const float* org, const float* dir,
                  const float* tmax, int32_t n, float* t_out, int32_t* out, int* gstack, unsigned long long* hits,
                  int force_exact);
-// One launch over the `rows` x cam->res[0] pixels of a part (prm: seed and partition, validated by
-// the caller); `out` holds device pointers, NULL = channel skipped.
-int aov_launch(void* stream, const QueryScene& sc, const QueryPlan& plan, const pt_camera* cam, const pt_params* prm,
-               int32_t rows, int32_t sample, const pt_aov* out, int* gstack, unsigned long long* hits,
+// One launch over the pixels of a part (shape: part_shape of cam and prm, pt_launch.h); `out` holds device pointers, NULL = channel skipped.
+int aov_launch(void* stream, const QueryScene& sc, const WalkPlan& plan, const pt_camera* cam, const pt_params* prm,
+               const PartShape& shape, int32_t sample, const pt_aov* out, int* gstack, unsigned long long* hits,
                int force_exact);
 
 // ---- trace() on caller-supplied rays (pt_paths.hip; the entry point is in pt_kernel.hip) ----
-// Where a launch keeps the scene, the walk's stack and the path records, and its grid (paths_plan).
-struct PathsPlan {
-    int lds_scene, lds_stack, lds_rec;  // 1: in LDS; 0: read through L1/L2 / rows in a global buffer
-    int rows;                           // stack rows per lane = max(1, tree depth)
-    int rec;                            // path records per lane = depth - 1
-    int grid;                           // blocks of kBlock lanes
-    size_t lds_bytes;                   // dynamic LDS per block
-    size_t stack_ints;                  // ints the global stack buffer must hold (0 with the stack in LDS)
-    size_t rec_words;                   // 32-bit words EACH of the two global record arrays must hold
-};
 // `items`: rays x samples of the largest launch; depth >= 1.
-int paths_plan(const QueryScene& sc, size_t lds_usable, int num_cus, int depth, int64_t items, PathsPlan& plan);
+int paths_plan(const QueryScene& sc, size_t lds_usable, int num_cus, int depth, int64_t items, WalkPlan& plan);
 // One launch over m rays x spp samples (device pointers; m * spp < 2^31); no synchronisation.
 struct PathsLaunch {
     const float* org;         // m x 3
@@ -186,6 +178,6 @@ struct PathsLaunch {
     const void* theta_tab;    // the device's theta table (float2), or nullptr
     int theta_lanes, dark, force_exact;
 };
-int paths_launch(void* stream, const QueryScene& sc, const PathsPlan& plan, const PathsLaunch& l);
+int paths_launch(void* stream, const QueryScene& sc, const WalkPlan& plan, const PathsLaunch& l);
 
 }  // namespace pt

@@ -16,7 +16,7 @@
 // finish in any order in any wave, and float addition in sample order is the contract.
 //
 // shade and finish_path read kernarg_args(): the FIRST kernel argument as TraceArgs (depth,
-// rec_size, dark, flags, theta_tab, theta_lanes). paths_launch fills those as pt_ctx_render does.
+// rec_size, dark, flags, theta_tab, theta_lanes). paths_launch fills those as a render does (the pool by pool_sizing, pt_launch.h).
 //
 // Slab-form gate: the IEEE min/max slab form needs every lane's origin and inverse direction
 // finite and bounded (query_ray_bounded). A caller's origin can be NaN or inf, and after such a
@@ -39,15 +39,13 @@
 
 #include <algorithm>
 
-#include "pt_internal.h"
+#include "pt_launch.h"
 #include "pt_raygate.h"
 #include "pt_trace.h"
 
 namespace pt {
 
 static_assert(kSpecularIterBound == kMaxSpecularIters, "host and device bound of the specular rejection loop");
-
-FastDiv fastdiv_for(uint32_t d);  // make_fastdiv (pt_kernel.hip)
 
 struct PathArgs {
     const float* __restrict__ org;        // m x 3
@@ -156,54 +154,24 @@ PathsKernel paths_kernel(bool lds_scene, bool lds_stack, bool lds_rec) {
                      : (lds_stack ? paths_kernel_t<false, true>(lds_rec) : paths_kernel_t<false, false>(lds_rec));
 }
 
-size_t lds_round(size_t b) { return (b + kLdsGranule - 1) / kLdsGranule * kLdsGranule; }
-
 }  // namespace
 
-// Placement, by query_plan's rules (pt_query.hip) and hooks: the stack rows go to LDS when they
-// leave two blocks per CU and stay inside 64 KiB; nodes, triangles and (here) materials when
-// they fit PT_LDS_SCENE_BYTES' budget and the same bounds beside the stack; then the path
-// records, depth - 1 rows of kBlock x 8 B, when they still fit beside both (PT_TRACE_LDS_REC=0,
-// test hook, forces the global buffer). Whatever does not fit is read and written through L1/L2,
-// so every depth up to PT_MAX_DEPTH runs.
-int paths_plan(const QueryScene& sc, size_t lds_usable, int num_cus, int depth, int64_t items, PathsPlan& plan) {
-    const size_t cap = std::min<size_t>(64 * 1024, lds_usable / 2);
-    plan.rows = std::max(1, sc.tree_depth);
-    plan.rec = std::max(0, depth - 1);
-    const size_t stack_b = sizeof(int) * (size_t)kBlock * plan.rows;
-    const char* ls = hook_env("PT_QUERY_LDS_STACK");
-    plan.lds_stack = !(ls && *ls == '0') && lds_round(stack_b) <= cap;
-    const size_t scene_b = sizeof(float4) * (2 * (size_t)sc.num_nodes + 5 * (size_t)sc.num_tris);
-    const char* le = hook_env("PT_LDS_SCENE_BYTES");
-    const size_t budget = (le && *le) ? (size_t)strtoull(le, nullptr, 0) : 32 * 1024;  // lds_scene_budget (pt_kernel.hip)
-    size_t used = plan.lds_stack ? stack_b : 0;
-    plan.lds_scene = scene_b <= budget && lds_round(scene_b + used) <= cap;
-    used += plan.lds_scene ? scene_b : 0;
-    const size_t rec_b = 2 * sizeof(int) * (size_t)kBlock * plan.rec;
-    const char* lr = hook_env("PT_TRACE_LDS_REC");
-    plan.lds_rec = !(lr && *lr == '0') && lds_round(used + rec_b) <= cap;
-    used += plan.lds_rec ? rec_b : 0;
-    plan.lds_bytes = used;
-    int per_cu = 0;
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &per_cu, (const void*)paths_kernel(plan.lds_scene, plan.lds_stack, plan.lds_rec), kBlock, plan.lds_bytes);
-    if (e != hipSuccess) return set_error(PT_E_HIP, "trace occupancy failed: %s", hipGetErrorString(e));
-    // the occupancy query can be optimistic about LDS (kLdsUsable, pt_internal.h)
-    if (plan.lds_bytes > 0 && lds_usable > 0) per_cu = std::min<int>(per_cu, (int)(lds_usable / lds_round(plan.lds_bytes)));
-    per_cu = std::max(1, per_cu);
-    const int64_t blocks = (items + kBlock - 1) / kBlock;
-    plan.grid = (int)std::max<int64_t>(1, std::min<int64_t>(blocks, (int64_t)per_cu * std::max(1, num_cus)));
-    plan.stack_ints = plan.lds_stack ? 0 : (size_t)plan.grid * plan.rows * kBlock;
-    plan.rec_words = plan.lds_rec ? 0 : (size_t)plan.grid * plan.rec * kBlock;
-    return PT_OK;
+// Placement and grid by the binary walk's shared rules (pt_launch.h: place_walk, plan_grid): the
+// stack rows, then nodes, triangles and (here) materials, 5 float4 per triangle, then the path
+// records, depth - 1 rows. Whatever does not fit is read and written through L1/L2, so every
+// depth up to PT_MAX_DEPTH runs.
+int paths_plan(const QueryScene& sc, size_t lds_usable, int num_cus, int depth, int64_t items, WalkPlan& plan) {
+    place_walk_hooked(sc.num_nodes, sc.num_tris, sc.tree_depth, 5, std::max(0, depth - 1), lds_usable, true, plan);
+    return walk_grid((const void*)paths_kernel(plan.lds_scene, plan.lds_stack, plan.lds_rec), lds_usable, num_cus, items,
+                     plan, "trace");
 }
 
-int paths_launch(void* stream, const QueryScene& sc, const PathsPlan& plan, const PathsLaunch& l) {
+int paths_launch(void* stream, const QueryScene& sc, const WalkPlan& plan, const PathsLaunch& l) {
     const unsigned long long total = (unsigned long long)l.m * (unsigned long long)l.spp;
     if (l.m <= 0 || l.spp <= 0 || l.depth <= 0 || total >= (1ull << 31))
         return set_error(PT_E_ARG, "trace launch of %d rays x %d samples, depth %d", l.m, l.spp, l.depth);
     const int grid = (int)std::min<unsigned long long>((unsigned long long)plan.grid, (total + kBlock - 1) / kBlock);
-    // every field shade, finish_path and claim_item read, as pt_ctx_render fills them
+    // every field shade, finish_path and claim_item read, as fill_trace_args (pt_kernel.hip) fills them
     TraceArgs A;
     memset(&A, 0, sizeof(A));
     A.nodes = reinterpret_cast<const float4*>(sc.nodes);
@@ -224,20 +192,16 @@ int paths_launch(void* stream, const QueryScene& sc, const PathsPlan& plan, cons
     A.num_tri4 = 3 * sc.num_tris;
     A.num_mat4 = 2 * sc.num_tris;
     A.force_exact_slab = l.force_exact;
-    A.div_npix = fastdiv_for((uint32_t)l.m);
+    A.div_npix = make_fastdiv((uint32_t)l.m);
     A.theta_tab = reinterpret_cast<const float2*>(l.theta_tab);
     A.theta_lanes = l.theta_tab ? l.theta_lanes : 0;  // no table: the computed form in every wave
     A.dark = l.dark;
     A.flags = nullptr;  // dense slab: every path stores its record
-    // Refills (pt_ctx_render's rules for the tree walk): about 128 per wave, 128 to kChunk items
-    // each; every wave starts with a static range, the whole even share in a small launch.
-    const unsigned long long waves = (unsigned long long)grid * (kBlock / kWave);
-    A.chunk = (int)std::max<unsigned long long>(kWave, std::min<unsigned long long>(kChunk, std::max<unsigned long long>(128, total / (waves * 128))));
-    const unsigned long long share = total / waves;
-    unsigned long long st = std::min<unsigned long long>((unsigned long long)A.chunk, share);
-    if (share < 4ull * kChunk) st = share;
-    A.static_items = (uint32_t)st;
-    A.static_base = waves * st;  // <= total < 2^31
+    // the work pool by a render's rule for the tree walk (refills of 128 to kChunk items)
+    const PoolSizing pool = pool_sizing(total, grid, 128);
+    A.chunk = pool.chunk;
+    A.static_items = pool.static_items;
+    A.static_base = pool.static_base;
     A.acc_chunks = 0;            // no fused accumulation: the sum is a pass of its own
 
     PathArgs P{};

@@ -27,13 +27,11 @@
 
 #include <algorithm>
 
-#include "pt_internal.h"
+#include "pt_launch.h"
 #include "pt_raygate.h"
 #include "pt_trace.h"
 
 namespace pt {
-
-FastDiv fastdiv_for(uint32_t d);  // make_fastdiv (pt_kernel.hip)
 
 // intersect_tree's walk, stopping at the first triangle hit with t < tmax (see above).
 template <bool kFiniteInv, typename NodePtr, typename TriPtr>
@@ -251,9 +249,7 @@ const void* plan_kernel(int which, bool lds_scene, bool lds_stack) {
                         : (const void*)query_kernel_t<false>(lds_scene, lds_stack);
 }
 
-size_t lds_round(size_t b) { return (b + kLdsGranule - 1) / kLdsGranule * kLdsGranule; }
-
-QueryArgs query_args(const QueryScene& sc, const QueryPlan& plan, int* gstack, unsigned long long* hits,
+QueryArgs query_args(const QueryScene& sc, const WalkPlan& plan, int* gstack, unsigned long long* hits,
                      int force_exact) {
     QueryArgs Q{};
     Q.nodes = reinterpret_cast<const float4*>(sc.nodes);
@@ -271,36 +267,14 @@ QueryArgs query_args(const QueryScene& sc, const QueryPlan& plan, int* gstack, u
 
 }  // namespace
 
-// Placement. The stack rows go to LDS when a block's kBlock * rows * 4 B leave at least two
-// blocks per CU within the usable LDS and stay inside the 64 KiB a launch gets without an
-// opt-in; otherwise to the global buffer (PT_QUERY_LDS_STACK=0, test hook, forces that). Nodes
-// and triangles are staged in LDS when they fit PT_LDS_SCENE_BYTES' budget and the same two
-// bounds beside the stack; otherwise they are read through L1/L2.
-int query_plan(int which, const QueryScene& sc, size_t lds_usable, int num_cus, int64_t count, QueryPlan& plan) {
-    const size_t cap = std::min<size_t>(64 * 1024, lds_usable / 2);
-    plan.rows = std::max(1, sc.tree_depth);
-    const size_t stack_b = sizeof(int) * (size_t)kBlock * plan.rows;
-    const char* ls = hook_env("PT_QUERY_LDS_STACK");
-    plan.lds_stack = !(ls && *ls == '0') && lds_round(stack_b) <= cap;
-    const size_t scene_b = sizeof(float4) * (2 * (size_t)sc.num_nodes + 3 * (size_t)sc.num_tris);
-    const char* le = hook_env("PT_LDS_SCENE_BYTES");
-    const size_t budget = (le && *le) ? (size_t)strtoull(le, nullptr, 0) : 32 * 1024;  // lds_scene_budget (pt_kernel.hip)
-    plan.lds_scene = scene_b <= budget && lds_round(scene_b + (plan.lds_stack ? stack_b : 0)) <= cap;
-    plan.lds_bytes = (plan.lds_scene ? scene_b : 0) + (plan.lds_stack ? stack_b : 0);
-    int per_cu = 0;
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, plan_kernel(which, plan.lds_scene, plan.lds_stack),
-                                                                      kBlock, plan.lds_bytes);
-    if (e != hipSuccess) return set_error(PT_E_HIP, "query occupancy failed: %s", hipGetErrorString(e));
-    // the occupancy query can be optimistic about LDS (kLdsUsable, pt_internal.h)
-    if (plan.lds_bytes > 0 && lds_usable > 0) per_cu = std::min<int>(per_cu, (int)(lds_usable / lds_round(plan.lds_bytes)));
-    per_cu = std::max(1, per_cu);
-    const int64_t blocks = (count + kBlock - 1) / kBlock;
-    plan.grid = (int)std::max<int64_t>(1, std::min<int64_t>(blocks, (int64_t)per_cu * std::max(1, num_cus)));
-    plan.stack_ints = plan.lds_stack ? 0 : (size_t)plan.grid * plan.rows * kBlock;
-    return PT_OK;
+// Placement and grid by the binary walk's shared rules (pt_launch.h: place_walk, plan_grid): the
+// stack rows, then nodes and triangles (3 float4 each, no materials), no records.
+int query_plan(int which, const QueryScene& sc, size_t lds_usable, int num_cus, int64_t count, WalkPlan& plan) {
+    place_walk_hooked(sc.num_nodes, sc.num_tris, sc.tree_depth, 3, 0, lds_usable, false, plan);
+    return walk_grid(plan_kernel(which, plan.lds_scene, plan.lds_stack), lds_usable, num_cus, count, plan, "query");
 }
 
-int query_launch(void* stream, const QueryScene& sc, const QueryPlan& plan, int any, const float* org, const float* dir,
+int query_launch(void* stream, const QueryScene& sc, const WalkPlan& plan, int any, const float* org, const float* dir,
                  const float* tmax, int32_t n, float* t_out, int32_t* out, int* gstack, unsigned long long* hits,
                  int force_exact) {
     QueryArgs Q = query_args(sc, plan, gstack, hits, force_exact);
@@ -319,35 +293,13 @@ int query_launch(void* stream, const QueryScene& sc, const QueryPlan& plan, int 
     return PT_OK;
 }
 
-int aov_launch(void* stream, const QueryScene& sc, const QueryPlan& plan, const pt_camera* cam, const pt_params* prm,
-               int32_t rows, int32_t sample, const pt_aov* out, int* gstack, unsigned long long* hits,
+int aov_launch(void* stream, const QueryScene& sc, const WalkPlan& plan, const pt_camera* cam, const pt_params* prm,
+               const PartShape& shape, int32_t sample, const pt_aov* out, int* gstack, unsigned long long* hits,
                int force_exact) {
     const QueryArgs Q = query_args(sc, plan, gstack, hits, force_exact);
-    // the fields camera_ray and part_row read, as pt_ctx_render fills them
     TraceArgs A;
     memset(&A, 0, sizeof(A));
-    A.pos_x = cam->pos[0];
-    A.pos_y = cam->pos[1];
-    A.pos_z = cam->pos[2];
-    const float* T = cam->transform;
-    A.col0_x = T[0]; A.col0_y = T[3]; A.col0_z = T[6];
-    A.col1_x = T[1]; A.col1_y = T[4]; A.col1_z = T[7];
-    A.col2_x = T[2]; A.col2_y = T[5]; A.col2_z = T[8];
-    A.half_vres_x = cam->v_res[0] / 2.0f;
-    A.half_vres_y = cam->v_res[1] / 2.0f;
-    A.cell = cam->cell_size;
-    A.cz_col0 = -cam->distance * A.col0_z;
-    A.cz_col1 = -cam->distance * A.col1_z;
-    A.cz_col2 = -cam->distance * A.col2_z;
-    A.W = cam->res[0];
-    A.npix = rows * cam->res[0];
-    A.part_index = prm->part_index;
-    A.part_count = prm->part_count > 0 ? prm->part_count : 1;
-    A.band_rows = prm->band_rows > 0 ? prm->band_rows : 1;
-    A.seed = prm->seed;
-    A.div_npix = fastdiv_for((uint32_t)std::max(A.npix, 1));
-    A.div_w = fastdiv_for((uint32_t)A.W);
-    A.div_band = fastdiv_for((uint32_t)A.band_rows);
+    fill_camera(A, cam, shape, prm);  // the fields camera_ray and part_row read
     const AovOut O{out->t, out->tri, out->normal, out->albedo, out->emission, out->ray};
     const int grid = (int)std::min<int64_t>(plan.grid, ((int64_t)A.npix + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(aov_kernel(plan.lds_scene, plan.lds_stack), dim3(grid), dim3(kBlock), plan.lds_bytes,

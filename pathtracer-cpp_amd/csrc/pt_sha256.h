@@ -1,5 +1,5 @@
 // pt_sha256.h — SHA-256 (FIPS 180-4) for the on-disk hipRTC code-object cache keys and
-// payload checks (pt_kernel.hip: rtc disk cache). Host code only; no library dependency.
+// payload checks (pt_rtc.hip: rtc disk cache). Host code only; no library dependency.
 #pragma once
 
 #include <stddef.h>

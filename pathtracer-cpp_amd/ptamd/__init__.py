@@ -344,6 +344,17 @@ class Renderer:
         return {"albedo_x2": bool(out[0]), "specular": bool(out[1]), "rtc": bool(out[2]), "wide_nodes": out[3],
                 "dark": bool(out[4])}
 
+    PLAN_KEYS = ("kernel_path", "flat", "wide", "pairs", "pair_queue", "lds_bytes", "lds_scene", "wide_rows",
+                 "wide_queue", "wide_top", "blocks_per_cu", "batch", "per_item", "fused", "tail", "flags_pm",
+                 "trace_launches", "regen_thresh", "theta_lanes", "grid", "chunk", "static_items", "acc_every",
+                 "num_cus")
+
+    def plan(self) -> dict:
+        """The launch plan of this context's last render (test hook pt_debug_ctx_plan)."""
+        out = (C.c_int64 * len(self.PLAN_KEYS))()
+        check(lib().pt_debug_ctx_plan(self.h, out))
+        return dict(zip(self.PLAN_KEYS, list(out)))
+
     def set_scene(self, bvh: BVH) -> None:
         ref = _SceneRef(bvh)
         check(lib().pt_ctx_set_scene(self.h, C.byref(ref.s)))

@@ -29,7 +29,7 @@ EXPORTED = (
     "pt_debug_rccl_failover", "pt_debug_rtc_cache", "pt_devices_release", "pt_debug_ctx_flags", "pt_debug_counter",
     "pt_debug_scene_dark", "pt_debug_rtc_start", "pt_debug_pack_hash",
     "pt_bvh_intersect", "pt_ctx_intersect", "pt_ctx_render_aov",
-    "pt_bvh_trace", "pt_ctx_trace",
+    "pt_bvh_trace", "pt_ctx_trace", "pt_debug_ctx_plan", "pt_debug_walk_placement",
 )
 PT_MAX_DEVICES = 16
 
@@ -217,6 +217,10 @@ def lib() -> C.CDLL:
             L.pt_devices_release.restype = None
         if hasattr(L, "pt_debug_ctx_flags"):
             L.pt_debug_ctx_flags.argtypes = [P, P]
+        if hasattr(L, "pt_debug_ctx_plan"):
+            L.pt_debug_ctx_plan.argtypes = [P, P]
+        if hasattr(L, "pt_debug_walk_placement"):
+            L.pt_debug_walk_placement.argtypes = [C.c_int32] * 5 + [C.c_uint64, P]
         if hasattr(L, "pt_debug_scene_dark"):
             L.pt_debug_scene_dark.argtypes = [C.POINTER(pt_scene)]
         if hasattr(L, "pt_debug_pack_hash"):

@@ -54,7 +54,7 @@ def test_library_exports_every_declared_symbol(pt):
 
 
 def test_dark_gate_needs_finite_cos_theta(pt):
-    """The dark-path gate (pt_kernel.hip scene_dark) also requires every path's
+    """The dark-path gate (pt_launch.hip scene_dark) also requires every path's
     cos theta to be finite (VERDICT r5 finding 1): SPECULAR roughness |r| <= 1.15, so that
     specular_sample's refl + j (material.h:15-25) never cancels, and unit-length shading normals
     (a collinear or underflowing sliver normalises to NaN, triangle.h:45-49)."""
@@ -305,7 +305,7 @@ def _rtc_source(pt, bvh):
 def test_rtc_albedo_x2_gate(pt, monkeypatch, case, on):
     """The flat kernel unwinds with pre-doubled albedo (finish_path<., true>) only when the
     host can bound the radiance below 2^125 over PT_MAX_DEPTH levels with every material
-    finite (pt_kernel.hip: albedo_x2_ok); otherwise it keeps (2L) * albedo."""
+    finite (pt_launch.hip: albedo_x2_ok); otherwise it keeps (2L) * albedo."""
     from ptamd import scenes
     b = pt.BVH.from_scene(scene_for("modified_cornell_r0.3" if case == "mcornell" else "cornell", (8, 8)))
     scale = {"emit_2^100": ("emit", 2.0 ** 100), "albedo_2^127": ("color", 2.0 ** 127),
@@ -521,7 +521,7 @@ def test_rccl_failed_group_aborts_its_communicators(pt, fail_step, n_devices):
 
 
 def test_rtc_disk_cache_reuses_and_rejects_corrupt_entries(pt, tmp_path, monkeypatch):
-    """The scene kernel's on-disk code-object cache (pt_kernel.hip): a compile is stored
+    """The scene kernel's on-disk code-object cache (pt_rtc.hip): a compile is stored
     under sha256(source, device headers, options, hipRTC version); a later request (here:
     after this process forgets its own compiles) loads the verified entry instead of
     compiling; a corrupted, truncated or foreign entry is rejected, recompiled and

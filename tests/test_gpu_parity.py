@@ -361,7 +361,7 @@ def _bits_equal_nan(a, b):
 @pytest.mark.parametrize("depth", [5, 8])
 def test_albedo_x2_unwinding_bitexact(ptamd_mod, monkeypatch, case, x2, depth):
     """The hipRTC flat kernel's unwinding with pre-doubled albedo (L * 2a instead of
-    (2L) * a; enabled by the host's radiance bound, pt_kernel.hip: albedo_x2_ok) and without
+    (2L) * a; enabled by the host's radiance bound, pt_launch.hip: albedo_x2_ok) and without
     it: the oracle's bits and ray count at depth 5 (records loaded up front) and 8 (the
     per-level loop), with large emission (2^50: still enabled; 2^100: bound fails, off;
     2^126: the reference's 2L overflows to inf where L * 2a would not), an albedo of 2^127

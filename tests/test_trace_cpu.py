@@ -14,6 +14,7 @@ import _oracle as O
 import _reftrace as RT
 import _refwalk as RW
 import _treecases as TC
+from _plans import _planned
 from conftest import ROOT
 
 PKG = os.path.join(ROOT, "pathtracer-cpp_amd")
@@ -202,3 +203,72 @@ def test_dropin_cpp_trace(tmp_path, name):
     # trace_batch(): per-ray streams pt_sample_seed(i, 0, seed)
     want, _, _ = RT.trace(nodes, idx, verts, mtype, mvals, o, d, RT.sample_seeds(n, 1, seed)[:, 0], depth)
     RT.assert_same(got[:, 3:6], want, "drop-in trace_batch()")
+
+
+def _placement(nodes, tris, tree_depth, tri_f4, rec_rows, lds_usable=161280):
+    import ptamd
+    out = (C.c_int32 * 4)()
+    ptamd.check(ptamd.lib().pt_debug_walk_placement(nodes, tris, tree_depth, tri_f4, rec_rows, lds_usable, out))
+    return {"lds_scene": out[0], "lds_stack": out[1], "lds_records": out[2]}, out[3]
+
+
+def _want(nodes, tris, tree_depth, tri_f4, rec_rows, lds_usable=161280, **rule):
+    return _planned({"nodes": nodes, "tree_depth": tree_depth}, tris, rec_rows + 1, lds_usable=lds_usable, tri_f4=tri_f4,
+                    **rule)
+
+
+# (nodes, triangles, tree depth, float4 per triangle, record rows): (scene, stack, records) in LDS.
+# With 161,280 B of LDS per CU the cap is 65,536 B: 64 stack rows of 1,024 B fill it (no room
+# for the 256-B scene beside them), 65 do not;
+# 16 (2 * 24 + 5 * 400) = 32,768 B of scene is the default budget, one node more is over it;
+# beside an 8-row stack (8,192 B) and no scene, 28 record rows of 2,048 B fit, 29 do not.
+BOUNDARIES = [((3, 2, 64, 5, 0), (0, 1, 1)), ((3, 2, 65, 5, 0), (1, 0, 1)),
+              ((24, 400, 8, 5, 0), (1, 1, 1)), ((25, 400, 8, 5, 0), (0, 1, 1)),
+              ((1000, 1000, 8, 5, 28), (0, 1, 1)), ((1000, 1000, 8, 5, 29), (0, 1, 0))]
+
+
+@pytest.mark.parametrize("shape,flags", BOUNDARIES)
+def test_walk_placement_boundaries(shape, flags, monkeypatch):
+    """place_walk (pt_launch.hip), the one placement rule of the ray queries and pt_ctx_trace,
+    against its restatement tests/_plans.py::_planned at the sizes where each part stops fitting."""
+    for hook in ("PT_LDS_SCENE_BYTES", "PT_QUERY_LDS_STACK", "PT_TRACE_LDS_REC"):
+        monkeypatch.delenv(hook, raising=False)
+    if shape[4] >= 28:
+        monkeypatch.setenv("PT_LDS_SCENE_BYTES", "0")  # a zero scene budget: stack and records only
+    rule = dict(scene_budget=0) if shape[4] >= 28 else {}
+    got, lds_bytes = _placement(*shape)
+    assert got == _want(*shape, **rule)
+    assert (got["lds_scene"], got["lds_stack"], got["lds_records"]) == flags
+    nodes, tris, depth, tri_f4, rec = shape
+    assert lds_bytes == (got["lds_scene"] * 16 * (2 * nodes + tri_f4 * tris) + got["lds_stack"] * 1024 * depth +
+                         got["lds_records"] * 2048 * rec)
+    assert lds_bytes <= 65536
+
+
+def test_walk_placement_usable_lds_and_hooks(monkeypatch):
+    for hook in ("PT_LDS_SCENE_BYTES", "PT_QUERY_LDS_STACK", "PT_TRACE_LDS_REC"):
+        monkeypatch.delenv(hook, raising=False)
+    # 65,536 B per CU halve the cap: 32 stack rows fit, 33 do not; the scene no longer fits beside them
+    for depth, stack in ((32, 1), (33, 0)):
+        got, _ = _placement(24, 400, depth, 5, 4, 65536)
+        assert got == _want(24, 400, depth, 5, 4, 65536) and got["lds_stack"] == stack and got["lds_scene"] == 1 - stack
+    # no usable LDS: nothing is placed there
+    got, lds_bytes = _placement(24, 400, 8, 5, 4, 0)
+    assert got == _want(24, 400, 8, 5, 4, 0) == {"lds_scene": 0, "lds_stack": 0, "lds_records": 0} and lds_bytes == 0
+    # 3 float4 per triangle (queries) fit the budget where 5 (with materials) do not
+    assert _placement(24, 600, 8, 3, 0)[0]["lds_scene"] == 1 and _placement(24, 600, 8, 5, 0)[0]["lds_scene"] == 0
+    assert _placement(24, 600, 8, 3, 0)[0] == _want(24, 600, 8, 3, 0)
+    assert _placement(24, 600, 8, 5, 0)[0] == _want(24, 600, 8, 5, 0)
+    shape = (24, 600, 8, 5, 4)
+    for hook, value, rule, off in (("PT_QUERY_LDS_STACK", "0", dict(stack=False), "lds_stack"),
+                                   ("PT_TRACE_LDS_REC", "0", dict(rec=False), "lds_records"),
+                                   ("PT_LDS_SCENE_BYTES", "0", dict(scene_budget=0), "lds_scene"),
+                                   ("PT_LDS_SCENE_BYTES", "65536", dict(scene_budget=65536), None)):
+        monkeypatch.setenv(hook, value)
+        got, _ = _placement(*shape)
+        monkeypatch.delenv(hook)
+        assert got == _want(*shape, **rule), (hook, value)
+        if off:
+            assert got[off] == 0
+        else:
+            assert got["lds_scene"] == 1 and _placement(*shape)[0]["lds_scene"] == 0  # 16 * 3,048 B: over 32 KiB only

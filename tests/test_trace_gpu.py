@@ -8,6 +8,7 @@ import _oracle as O
 import _reftrace as RT
 import _refwalk as RW
 import _treecases as TC
+from _plans import _planned
 
 pytestmark = pytest.mark.gpu
 
@@ -73,22 +74,6 @@ def test_arbitrary_rays_match_restatement(renderers, name):
         assert st_h["rays"] == st["rays"]
     if name == "cornell":
         assert st["lds_scene"] == 1 and st["lds_stack"] == 1 and st["lds_records"] == 1
-
-
-def _planned(info, ntris, depth, scene_budget=32 * 1024, stack=True, rec=True):
-    """pt_paths.hip's placement rule restated: stack rows, then the scene, then the records go to
-    LDS while they fit 64 KiB (in 256-byte granules)."""
-    cap = 64 * 1024
-    rnd = lambda b: -(-b // 256) * 256  # noqa: E731
-    stack_b = 4 * 256 * max(1, info["tree_depth"])
-    scene_b = 16 * (2 * info["nodes"] + 5 * ntris)
-    rec_b = 8 * 256 * (depth - 1)
-    lds_stack = stack and rnd(stack_b) <= cap
-    used = stack_b if lds_stack else 0
-    lds_scene = scene_b <= scene_budget and rnd(scene_b + used) <= cap
-    used += scene_b if lds_scene else 0
-    lds_rec = rec and rnd(used + rec_b) <= cap
-    return {"lds_scene": int(lds_scene), "lds_stack": int(lds_stack), "lds_records": int(lds_rec)}
 
 
 PLACEMENTS = [("PT_LDS_SCENE_BYTES", "0", dict(scene_budget=0)),
