@@ -11,6 +11,7 @@
  *                                     trace()       render.h:36-61
  *   pt_bvh_intersect / pt_ctx_intersect <- BVH::intersect() bvh.h:156-183 (batched; closest and any hit)
  *   pt_bvh_trace / pt_ctx_trace <- trace() render.h:36-61 (batched, caller's rays)
+ *   pt_bvh_trace_grad / pt_ctx_trace_grad: its exact gradient w.r.t. color and emit_color
  *   pt_ctx_render_aov                <- Camera::get_ray camera.h:63-73 + BVH::intersect + Triangle::normal
  *                                       triangle.h:45-49 (the first hit of a sample, per pixel)
  *   pt_bvh_build                     <- BVH::build()  bvh.h:79-155 (find_best_axis 48-78)
@@ -370,6 +371,63 @@ int pt_bvh_trace(const pt_scene* scene, const float* origins, const float* dirs,
  * Synchronous, and leaves a progressive sum as it is. */
 int pt_ctx_trace(pt_ctx* ctx, const float* origins, const float* dirs, int64_t n,
                  const pt_trace_params* params, float* rgb_out, int is_device, pt_trace_stats* stats);
+
+/* ---- material gradients of trace() along caller-supplied rays -------------------
+ * trace() draws its directions from the normal, the incoming direction and the roughness only
+ * (material.h:6-25), so a path's geometry does not depend on color or emit_color and the radiance
+ * is a polynomial in them, L_k = emit_k + ((2 L_{k+1}) color_k) cos_k (render.h:60): the
+ * derivative below is exact, without reparameterisation or bias. One call evaluates the radiance
+ * at (optionally) changed colours and emissions and/or back-propagates dLoss/d rgb_out to them.
+ * Material type and roughness always come from the scene; rays, spp, depth, seed and states are
+ * pt_ctx_trace's.
+ *
+ * Forward: rgb_out is bit-identical to pt_ctx_trace on a scene whose materials carry the override
+ * values (no override: to pt_ctx_trace itself), the in-order float32 sum over samples included.
+ *
+ * Per-path terms: float32, no contraction, in this operation order per channel. Path (i, s) has
+ * bounces k = 0 .. K-1 on triangles h_k with cosines c_k, then a terminal (an EMIT hit, a hit on
+ * the last allowed segment, or a miss). w = grad_rgb[i] / (float)spp; T_0 = w,
+ * T_{k+1} = ((2 T_k) color_{h_k}) c_k; L_{k+1} is the unwinding's value below bounce k (the
+ * forward bits). In ascending k: bounce k adds T_k to grad_emit[h_k] and ((2 T_k) L_{k+1}) c_k
+ * to grad_color[h_k]; a terminal that is a hit adds T_K to grad_emit[h_K] (and nothing to
+ * grad_color: its factor is trace(depth 0) = 0); a miss adds nothing. Indices are the caller's
+ * triangle indices: a triangle that sits in several leaves of a caller-built tree gets one sum.
+ *
+ * Sum: each destination is the sum of its float32 terms in float64, in any order (so within
+ * gamma_{N-1} sum|t| of the exact sum of its N terms); a call with n = 1, spp = 1 adds in k order
+ * and is reproducible bit for bit. Non-finite rays or materials make the affected destinations
+ * non-finite; nothing else is promised for them. A scene's dark-path shortcut never drops a
+ * grad_emit term (a dark path still carries T_k != 0). */
+typedef struct pt_trace_grad_io {
+    const float* color;     /* optional, num_tris*3: albedo to evaluate at, caller's triangle order; NULL = the scene's */
+    const float* emit;      /* optional, num_tris*3: emit_color to evaluate at; NULL = the scene's        */
+    const float* grad_rgb;  /* n*3: dLoss/d rgb_out; required if grad_color or grad_emit is given (else ignored) */
+    float*  rgb_out;        /* optional, n*3: the forward value at these materials                         */
+    double* grad_color;     /* optional, num_tris*3: dLoss/d color, overwritten                            */
+    double* grad_emit;      /* optional, num_tris*3: dLoss/d emit_color, overwritten                       */
+} pt_trace_grad_io;
+
+typedef struct pt_grad_stats {
+    pt_trace_stats trace;   /* as pt_ctx_trace fills it */
+    uint64_t terms;         /* contributions added to the requested ones of grad_color, grad_emit (3 channels = 1 term) */
+    double grad_ms;         /* zeroing, override gather, flush: everything but the path kernel */
+    int32_t lds_table;      /* 1: per-block gradient table in LDS; 0: global atomics only */
+    int32_t reserved;
+} pt_grad_stats;
+
+/* On the context's scene. is_device != 0: the rays, params->states and every pointer in io are
+ * DEVICE pointers on the context's device (inputs left untouched), otherwise host pointers.
+ * n == 0 is PT_OK, launches nothing and zeroes the gradient outputs; depth 0 zeroes every output.
+ * Launches are cut as pt_ctx_trace cuts them; runaway loops are reported as it reports them.
+ * Synchronous; uses buffers of its own, so a progressive sum stays valid, and the override never
+ * reaches the scene. */
+int pt_ctx_trace_grad(pt_ctx* ctx, const float* origins, const float* dirs, int64_t n,
+                      const pt_trace_params* params, const pt_trace_grad_io* io, int is_device,
+                      pt_grad_stats* stats);
+/* The same terms on the host over the caller's own arrays (no device needed), summed in double in
+ * (ray, sample, k) order; rgb_out bit-identical to pt_bvh_trace at the override values. */
+int pt_bvh_trace_grad(const pt_scene* scene, const float* origins, const float* dirs, int64_t n,
+                      const pt_trace_params* params, const pt_trace_grad_io* io, pt_grad_stats* stats);
 
 /* Number of rows of part `part_index` for the given partition. */
 int32_t pt_part_rows(int32_t res_y, int32_t part_index, int32_t part_count, int32_t band_rows);

@@ -1177,6 +1177,143 @@ int pt_bvh_trace(const pt_scene* scene, const float* origins, const float* dirs,
     return PT_OK;
 }
 
+// Material gradients of trace() on the host (pt_hip.h: the per-path terms): pt_bvh_trace's walk
+// with colour and emission taken from the override arrays, the unwinding kept per level
+// (L_{k+1}), then the throughput pass. Terms are added in double in (ray, sample, k) order.
+int pt_bvh_trace_grad(const pt_scene* scene, const float* origins, const float* dirs, int64_t n,
+                      const pt_trace_params* prm, const pt_trace_grad_io* io, pt_grad_stats* stats) {
+    const auto t_start = std::chrono::steady_clock::now();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!prm) return set_error(PT_E_ARG, "pt_bvh_trace_grad: params is NULL");
+    if (!io) return set_error(PT_E_ARG, "pt_bvh_trace_grad: io is NULL");
+    if (n < 0) return set_error(PT_E_ARG, "pt_bvh_trace_grad: n = %lld is negative", (long long)n);
+    if (prm->depth < 0 || prm->depth > PT_MAX_DEPTH)
+        return set_error(PT_E_ARG, "pt_bvh_trace_grad: depth %d outside 0..%d", prm->depth, PT_MAX_DEPTH);
+    if (prm->spp < 1 || prm->spp > kTraceMaxSpp)
+        return set_error(PT_E_ARG, "pt_bvh_trace_grad: spp %d outside 1..%d", prm->spp, kTraceMaxSpp);
+    PackedScene ps;
+    const int rc = pack_scene(scene, ps);  // pt_scene_validate's checks: the walk cannot leave the arrays
+    if (rc) return rc;
+    const bool want_grad = io->grad_color || io->grad_emit;
+    if (want_grad && !io->grad_rgb && n > 0)
+        return set_error(PT_E_ARG, "pt_bvh_trace_grad: grad_rgb is NULL but a gradient is asked for");
+    const size_t nt = (size_t)scene->num_tris;
+    if (io->grad_color) std::fill(io->grad_color, io->grad_color + 3 * nt, 0.0);
+    if (io->grad_emit) std::fill(io->grad_emit, io->grad_emit + 3 * nt, 0.0);
+    if (n == 0) return PT_OK;
+    if (!origins || !dirs) return set_error(PT_E_ARG, "pt_bvh_trace_grad: NULL argument");
+    std::vector<v3> color(nt), emit(nt);
+    for (size_t i = 0; i < nt; i++) {
+        const pt_material& m = scene->materials[i];
+        color[i] = io->color ? v3{io->color[3 * i], io->color[3 * i + 1], io->color[3 * i + 2]}
+                             : v3{m.color[0], m.color[1], m.color[2]};
+        emit[i] = io->emit ? v3{io->emit[3 * i], io->emit[3 * i + 1], io->emit[3 * i + 2]}
+                           : v3{m.emit[0], m.emit[1], m.emit[2]};
+    }
+    std::vector<int32_t> stack;
+    stack.reserve((size_t)ps.stack_size + 1);
+    const int depth = prm->depth, spp = prm->spp;
+    const float fs = (float)spp;
+    int32_t rec_tri[PT_MAX_DEPTH];
+    float rec_cos[PT_MAX_DEPTH];
+    v3 below[PT_MAX_DEPTH];  // L_{k+1}: the unwinding's value below bounce k
+    uint64_t rays = 0, runaway = 0, terms = 0;
+    auto add3 = [](double* dst, size_t tri, v3 t) {
+        dst[3 * tri] += (double)t.x;
+        dst[3 * tri + 1] += (double)t.y;
+        dst[3 * tri + 2] += (double)t.z;
+    };
+    for (int64_t r = 0; r < n; r++) {
+        float sum[3] = {0.0f, 0.0f, 0.0f};
+        for (int s = 0; s < spp; s++) {
+            Lcg g{prm->states ? prm->states[(size_t)r * spp + s] : pt_sample_seed((uint32_t)r, (uint32_t)s, prm->seed)};
+            v3 o{origins[3 * r], origins[3 * r + 1], origins[3 * r + 2]};
+            v3 d{dirs[3 * r], dirs[3 * r + 1], dirs[3 * r + 2]};
+            v3 L{0.0f, 0.0f, 0.0f};
+            int k = 0;
+            int32_t last = -1;  // the terminal's triangle, -1 a miss
+            while (k < depth) {  // depth == 0: trace() returns 0 (render.h:37)
+                float t;
+                rays++;
+                const int32_t ti = walk_ray(scene, stack, o, d, t);
+                if (ti < 0) break;  // miss -> 0
+                const pt_material& m = scene->materials[ti];
+                last = ti;
+                if (m.type == PT_MAT_EMIT) {
+                    L = emit[ti];
+                    break;
+                }
+                if (k + 1 >= depth) {  // trace(0) returns 0: emission + ((2 * 0) * albedo) * cos, no draw needed
+                    L = v3{emit[ti].x + 0.0f * color[ti].x, emit[ti].y + 0.0f * color[ti].y, emit[ti].z + 0.0f * color[ti].z};
+                    break;
+                }
+                const float* v = scene->verts + 9 * (size_t)ti;
+                const v3 v1{v[0], v[1], v[2]};
+                v3 nrm = normalize(cross(sub(v3{v[3], v[4], v[5]}, v1), sub(v3{v[6], v[7], v[8]}, v1)));
+                if (!(dot(nrm, d) < 0.0f)) nrm = neg(nrm);  // triangle.h:48
+                const v3 hp = add(o, scale(d, t));
+                v3 nd;
+                if (m.type == PT_MAT_SPECULAR) {
+                    if (!specular_dir(g, d, nrm, m.roughness, kSpecularIterBound, nd)) runaway++;
+                } else {
+                    nd = hemisphere_dir(g, nrm);
+                }
+                rec_tri[k] = ti;
+                rec_cos[k] = dot(nrm, nd);
+                o = add(hp, scale(nrm, 1e-4f));  // SHIFT_BIAS, render.h:16, 52
+                d = nd;
+                k++;
+                last = -1;
+            }
+            for (int j = k - 1; j >= 0; j--) {  // render.h:60
+                const v3 a = color[rec_tri[j]], e = emit[rec_tri[j]];
+                const float c = rec_cos[j];
+                below[j] = L;
+                L = v3{e.x + ((2.0f * L.x) * a.x) * c, e.y + ((2.0f * L.y) * a.y) * c, e.z + ((2.0f * L.z) * a.z) * c};
+            }
+            sum[0] = sum[0] + L.x;  // image.h:27-31
+            sum[1] = sum[1] + L.y;
+            sum[2] = sum[2] + L.z;
+            if (!want_grad) continue;
+            v3 T{io->grad_rgb[3 * r] / fs, io->grad_rgb[3 * r + 1] / fs, io->grad_rgb[3 * r + 2] / fs};
+            for (int j = 0; j < k; j++) {
+                const size_t tri = (size_t)rec_tri[j];
+                const v3 a = color[tri], b = below[j];
+                const float c = rec_cos[j];
+                if (io->grad_emit) {
+                    add3(io->grad_emit, tri, T);
+                    terms++;
+                }
+                if (io->grad_color) {
+                    add3(io->grad_color, tri, v3{((2.0f * T.x) * b.x) * c, ((2.0f * T.y) * b.y) * c, ((2.0f * T.z) * b.z) * c});
+                    terms++;
+                }
+                T = v3{((2.0f * T.x) * a.x) * c, ((2.0f * T.y) * a.y) * c, ((2.0f * T.z) * a.z) * c};
+            }
+            if (last >= 0 && io->grad_emit) {
+                add3(io->grad_emit, (size_t)last, T);
+                terms++;
+            }
+        }
+        if (io->rgb_out) {
+            io->rgb_out[3 * r] = sum[0] / fs;  // image.h:37-40
+            io->rgb_out[3 * r + 1] = sum[1] / fs;
+            io->rgb_out[3 * r + 2] = sum[2] / fs;
+        }
+    }
+    if (stats) {
+        stats->trace.rays = rays;
+        stats->trace.paths = (uint64_t)n * (uint64_t)spp;
+        stats->trace.runaway = runaway;
+        stats->terms = terms;
+        stats->trace.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    }
+    if (runaway != 0)
+        return set_error(PT_E_RUNAWAY, "%llu specular rejection loops hit the %d-iteration bound",
+                         (unsigned long long)runaway, kSpecularIterBound);
+    return PT_OK;
+}
+
 // Test hook: FNV-1a (64-bit) of every array and scalar pack_scene produces, so a change to the
 // packing's schedule (threads, order of work) can be checked to leave its output bit-identical.
 int pt_debug_pack_hash(const pt_scene* scene, uint64_t* hash) {

@@ -26,6 +26,7 @@
 
 #include <atomic>
 
+#include "pt_grad.h"
 #include "pt_hip_debug.h"
 #include "pt_launch.h"
 #include "pt_rtc.h"
@@ -310,6 +311,13 @@ struct pt_ctx {
     float* d_tstates = nullptr;              // staging of a host-pointer call's LCG states (uint32)
     size_t tstates_words = 0;
     unsigned long long* d_tctr = nullptr;    // work head, ray and runaway counters of a call (4 x u64)
+    // material gradients (pt_ctx_trace_grad): pt_ctx_trace's buffers, and
+    double* d_gtab = nullptr;                // the gradient table, 6 doubles per caller triangle, then the split outputs
+    size_t gtab_doubles = 0;
+    float4* d_gmats = nullptr;               // the per-call materials (override gathered), 2 per packed triangle
+    size_t gmats_f4 = 0;
+    float* d_gbuf = nullptr;                 // staging of a host-pointer call's override rows and grad_rgb
+    size_t gbuf_floats = 0;
     // progressive rendering: d_accum holds the running sum of prog_spp samples
     bool prog_valid = false;
     int prog_spp = 0;
@@ -1167,7 +1175,8 @@ void pt_ctx_destroy(pt_ctx* c) {
     for (void* p : {(void*)c->d_nodes, (void*)c->d_tris, (void*)c->d_mats, (void*)c->d_leaves, (void*)c->d_wide, (void*)c->d_wtris, (void*)c->d_nrm, (void*)c->d_umats, (void*)c->d_radiance, (void*)c->d_flags,
                     (void*)c->d_accum, (void*)c->d_out, (void*)c->d_ctr, (void*)c->d_stamps, (void*)c->d_rgb8, (void*)c->d_thr, (void*)c->d_xstack,
                     (void*)c->d_rank_tri, (void*)c->d_qstack, (void*)c->d_qbuf, (void*)c->d_qhits,
-                    (void*)c->d_tslab, (void*)c->d_trec, (void*)c->d_tbuf, (void*)c->d_tstates, (void*)c->d_tctr})
+                    (void*)c->d_tslab, (void*)c->d_trec, (void*)c->d_tbuf, (void*)c->d_tstates, (void*)c->d_tctr,
+                    (void*)c->d_gtab, (void*)c->d_gmats, (void*)c->d_gbuf})
         if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -1641,6 +1650,219 @@ int pt_ctx_trace(pt_ctx* c, const float* origins, const float* dirs, int64_t n, 
     HIP_TRY(hipMemcpyAsync(h_ctr, c->d_tctr, sizeof(h_ctr), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     finish(&plan, h_ctr, kernel_ms, reduce_ms, launches);
+    if (h_ctr[3] != 0)
+        return set_error(PT_E_RUNAWAY, "%llu specular rejection loops hit the %d-iteration bound", h_ctr[3],
+                         kMaxSpecularIters);
+    return PT_OK;
+}
+
+// Material gradients of trace() along the caller's rays (pt_grad.hip):
+// pt_ctx_trace's launches with pt_grad_kernel in place of pt_paths_kernel. Before them the
+// gradient table is zeroed and, with an override, the per-call materials are gathered; after
+// them the table is split into the caller's two arrays.
+int pt_ctx_trace_grad(pt_ctx* c, const float* origins, const float* dirs, int64_t n, const pt_trace_params* prm,
+                      const pt_trace_grad_io* io, int is_device, pt_grad_stats* stats) {
+    const auto t_start = std::chrono::steady_clock::now();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!c) return set_error(PT_E_ARG, "pt_ctx_trace_grad: context is NULL");
+    if (!prm) return set_error(PT_E_ARG, "pt_ctx_trace_grad: params is NULL");
+    if (!io) return set_error(PT_E_ARG, "pt_ctx_trace_grad: io is NULL");
+    if (n < 0) return set_error(PT_E_ARG, "pt_ctx_trace_grad: n = %lld is negative", (long long)n);
+    if (prm->depth < 0 || prm->depth > PT_MAX_DEPTH)
+        return set_error(PT_E_ARG, "pt_ctx_trace_grad: depth %d outside 0..%d", prm->depth, PT_MAX_DEPTH);
+    if (prm->spp < 1 || prm->spp > kTraceMaxSpp)
+        return set_error(PT_E_ARG, "pt_ctx_trace_grad: spp %d outside 1..%d", prm->spp, kTraceMaxSpp);
+    if (!c->have_scene) return set_error(PT_E_ARG, "pt_ctx_trace_grad: no scene set");
+    const bool want_grad = io->grad_color || io->grad_emit;
+    if (want_grad && !io->grad_rgb && n > 0)
+        return set_error(PT_E_ARG, "pt_ctx_trace_grad: grad_rgb is NULL but a gradient is asked for");
+    if (n > 0 && (!origins || !dirs)) return set_error(PT_E_ARG, "pt_ctx_trace_grad: NULL argument");
+    if (int rc0 = ctx_ready(c)) return rc0;
+    HIP_TRY(hipSetDevice(c->device));
+    const int32_t T = c->meta.num_tris;  // the caller's triangles (one tri_idx position each)
+    const size_t g_bytes = 3 * sizeof(double) * (size_t)T;
+    const int64_t spp = prm->spp;
+    auto zero_out = [&](void* p, size_t bytes) -> int {
+        if (!p) return PT_OK;
+        if (is_device) HIP_TRY(hipMemsetAsync(p, 0, bytes, c->stream));
+        else memset(p, 0, bytes);
+        return PT_OK;
+    };
+    auto finish = [&](const GradPlan* plan, const unsigned long long* ctr, double kms, double rms, double gms, int launches) {
+        if (!stats) return;
+        stats->trace.rays = ctr[1];
+        stats->trace.paths = (uint64_t)n * (uint64_t)spp;
+        stats->trace.runaway = ctr[3];
+        stats->trace.kernel_ms = kms;
+        stats->trace.reduce_ms = rms;
+        stats->trace.launches = launches;
+        stats->terms = ctr[2];
+        stats->grad_ms = gms;
+        if (plan) {
+            stats->trace.lds_scene = plan->walk.lds_scene;
+            stats->trace.lds_stack = plan->walk.lds_stack;
+            stats->trace.lds_records = plan->walk.lds_rec;
+            stats->lds_table = plan->lds_tab;
+        }
+        stats->trace.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    };
+    int rc;
+    if (n == 0 || prm->depth == 0) {  // no ray is traced: every output +0 (render.h:37)
+        if ((rc = zero_out(io->grad_color, g_bytes)) || (rc = zero_out(io->grad_emit, g_bytes))) return rc;
+        if (n > 0 && (rc = zero_out(io->rgb_out, 3 * sizeof(float) * (size_t)n))) return rc;
+        if (is_device) HIP_TRY(hipStreamSynchronize(c->stream));
+        const unsigned long long zero[4] = {0, 0, 0, 0};
+        finish(nullptr, zero, 0, 0, 0, 0);
+        return PT_OK;
+    }
+    // rays per launch, as pt_ctx_trace cuts them
+    int64_t m_max = std::min<int64_t>(n, ((1ll << 31) - 1) / spp);
+    m_max = std::min<int64_t>(m_max, (int64_t)(batch_bytes_budget(c->device, false) / (3 * sizeof(float) * (size_t)spp)));
+    if (!is_device) m_max = std::min(m_max, kQueryHostChunk);
+    if (const char* tc = hook_env("PT_TRACE_CHUNK"))
+        if (*tc) m_max = std::min<int64_t>(m_max, strtoll(tc, nullptr, 10));
+    m_max = std::max<int64_t>(m_max, 1);
+    const QueryScene sc = query_scene(c);
+    GradPlan plan;
+    if ((rc = grad_plan(sc, T, c->lds_usable, c->num_cus, prm->depth, m_max * spp, plan))) return rc;
+    if (plan.walk.stack_ints > 0 && (rc = ensure(&c->d_qstack, &c->qstack_ints, plan.walk.stack_ints))) return rc;
+    if (plan.walk.rec_words > 0 && (rc = ensure(&c->d_trec, &c->trec_words, 2 * plan.walk.rec_words))) return rc;
+    if ((rc = ensure(&c->d_tslab, &c->tslab_floats, 3 * (size_t)(m_max * spp)))) return rc;
+    if ((rc = ensure(&c->d_gtab, &c->gtab_doubles, 12 * (size_t)T))) return rc;  // table, then the split outputs
+    if (!c->d_tctr) HIP_TRY(hipMalloc((void**)&c->d_tctr, 4 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(c->d_tctr, 0, 4 * sizeof(unsigned long long), c->stream));
+    // host pointers: pt_ctx_trace's staging of the rays and results, and [color 3T][emit 3T][grad_rgb 3 m_max]
+    float *s_org = nullptr, *s_dir = nullptr, *s_out = nullptr, *s_grgb = nullptr;
+    const float *d_color = io->color, *d_emit = io->emit;
+    if (!is_device) {
+        if ((rc = ensure(&c->d_tbuf, &c->tbuf_floats, 9 * (size_t)m_max))) return rc;
+        s_org = c->d_tbuf;
+        s_dir = s_org + 3 * m_max;
+        s_out = s_dir + 3 * m_max;
+        if (prm->states && (rc = ensure(&c->d_tstates, &c->tstates_words, (size_t)(m_max * spp)))) return rc;
+        if ((rc = ensure(&c->d_gbuf, &c->gbuf_floats, 6 * (size_t)T + 3 * (size_t)m_max))) return rc;
+        s_grgb = c->d_gbuf + 6 * (size_t)T;
+    }
+    EventPair evg, evs, ev, ev2;
+    HIP_TRY(hipEventCreate(&evg.a));
+    HIP_TRY(hipEventCreate(&evg.b));
+    HIP_TRY(hipEventCreate(&evs.a));
+    HIP_TRY(hipEventCreate(&evs.b));
+    HIP_TRY(hipEventCreate(&ev.a));
+    HIP_TRY(hipEventCreate(&ev.b));
+    HIP_TRY(hipEventCreate(&ev2.a));
+    HIP_TRY(hipEventRecord(evg.a, c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_gtab, 0, 6 * sizeof(double) * (size_t)T, c->stream));
+    const f4* mats = sc.mats;
+    if (io->color || io->emit) {
+        if ((rc = ensure(&c->d_gmats, &c->gmats_f4, 2 * (size_t)T))) return rc;
+        if (!is_device) {
+            if (io->color) {
+                HIP_TRY(hipMemcpyAsync(c->d_gbuf, io->color, 3 * sizeof(float) * (size_t)T, hipMemcpyHostToDevice, c->stream));
+                d_color = c->d_gbuf;
+            }
+            if (io->emit) {
+                HIP_TRY(hipMemcpyAsync(c->d_gbuf + 3 * (size_t)T, io->emit, 3 * sizeof(float) * (size_t)T,
+                                       hipMemcpyHostToDevice, c->stream));
+                d_emit = c->d_gbuf + 3 * (size_t)T;
+            }
+        }
+        if ((rc = grad_gather_mats(c->stream, sc, d_color, d_emit, reinterpret_cast<f4*>(c->d_gmats)))) return rc;
+        mats = reinterpret_cast<const f4*>(c->d_gmats);
+    }
+    HIP_TRY(hipEventRecord(evg.b, c->stream));
+    GradLaunch gl{};
+    PathsLaunch& l = gl.p;
+    l.spp = (int32_t)spp;
+    l.depth = prm->depth;
+    l.seed = prm->seed;
+    l.slab = c->d_tslab;
+    l.ctr = c->d_tctr;
+    l.gstack = c->d_qstack;
+    l.grec = plan.walk.rec_words > 0 ? c->d_trec : nullptr;
+    l.dark = 0;
+    l.force_exact = query_force_exact();
+    {
+        const float2* tab = nullptr;
+        if ((rc = theta_choice(c, &l.theta_lanes, &tab))) return rc;
+        l.theta_tab = tab;
+    }
+    gl.mats = mats;
+    gl.table = c->d_gtab;
+    gl.table_rows = T;
+    gl.want_rgb = io->rgb_out ? 1 : 0;
+    gl.want_color = io->grad_color ? 1 : 0;
+    gl.want_emit = io->grad_emit ? 1 : 0;
+    double kernel_ms = 0, reduce_ms = 0, grad_ms = 0;
+    int launches = 0;
+    for (int64_t i0 = 0; i0 < n; i0 += m_max) {
+        const int32_t m = (int32_t)std::min(m_max, n - i0);
+        l.m = m;
+        l.ray_base = (uint32_t)i0;
+        l.org = origins + 3 * i0;
+        l.dir = dirs + 3 * i0;
+        l.states = prm->states ? prm->states + i0 * spp : nullptr;
+        gl.grad_rgb = want_grad ? io->grad_rgb + 3 * i0 : nullptr;
+        float* k_out = io->rgb_out ? io->rgb_out + 3 * i0 : nullptr;
+        if (!is_device) {
+            HIP_TRY(hipMemcpyAsync(s_org, l.org, 3 * sizeof(float) * (size_t)m, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(s_dir, l.dir, 3 * sizeof(float) * (size_t)m, hipMemcpyHostToDevice, c->stream));
+            if (prm->states) {
+                HIP_TRY(hipMemcpyAsync(c->d_tstates, l.states, sizeof(uint32_t) * (size_t)(m * spp), hipMemcpyHostToDevice,
+                                       c->stream));
+                l.states = reinterpret_cast<const uint32_t*>(c->d_tstates);
+            }
+            if (want_grad) {
+                HIP_TRY(hipMemcpyAsync(s_grgb, gl.grad_rgb, 3 * sizeof(float) * (size_t)m, hipMemcpyHostToDevice, c->stream));
+                gl.grad_rgb = s_grgb;
+            }
+            l.org = s_org;
+            l.dir = s_dir;
+            k_out = io->rgb_out ? s_out : nullptr;
+        }
+        HIP_TRY(hipMemsetAsync(c->d_tctr, 0, sizeof(unsigned long long), c->stream));  // work head only
+        HIP_TRY(hipEventRecord(ev.a, c->stream));
+        if ((rc = grad_launch(c->stream, sc, plan, gl))) return rc;
+        HIP_TRY(hipEventRecord(ev.b, c->stream));
+        if (k_out) {  // the ray's samples in order from +0, then / spp (image.h:27-31, 37-40)
+            hipLaunchKernelGGL(pt_accumulate_kernel, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->d_tslab,
+                               (float*)nullptr, k_out, (int)m, (int)spp, 1, 1, 0, (float)spp, (const uint32_t*)nullptr, 0);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(ev2.a, c->stream));
+        launches++;
+        if (!is_device && io->rgb_out)
+            HIP_TRY(hipMemcpyAsync(io->rgb_out + 3 * i0, s_out, 3 * sizeof(float) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
+        kernel_ms += ms;
+        HIP_TRY(hipEventElapsedTime(&ms, ev.b, ev2.a));
+        reduce_ms += ms;
+    }
+    // the table's rows into the caller's two arrays
+    HIP_TRY(hipEventRecord(evs.a, c->stream));
+    if (want_grad) {
+        double* o_color = io->grad_color ? (is_device ? io->grad_color : c->d_gtab + 6 * (size_t)T) : nullptr;
+        double* o_emit = io->grad_emit ? (is_device ? io->grad_emit : c->d_gtab + 9 * (size_t)T) : nullptr;
+        if ((rc = grad_split_table(c->stream, c->d_gtab, T, o_color, o_emit))) return rc;
+        if (!is_device) {
+            if (o_color) HIP_TRY(hipMemcpyAsync(io->grad_color, o_color, g_bytes, hipMemcpyDeviceToHost, c->stream));
+            if (o_emit) HIP_TRY(hipMemcpyAsync(io->grad_emit, o_emit, g_bytes, hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    HIP_TRY(hipEventRecord(evs.b, c->stream));
+    unsigned long long h_ctr[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h_ctr, c->d_tctr, sizeof(h_ctr), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, evg.a, evg.b));
+        grad_ms += ms;
+        HIP_TRY(hipEventElapsedTime(&ms, evs.a, evs.b));
+        grad_ms += ms;
+    }
+    finish(&plan, h_ctr, kernel_ms, reduce_ms, grad_ms, launches);
     if (h_ctr[3] != 0)
         return set_error(PT_E_RUNAWAY, "%llu specular rejection loops hit the %d-iteration bound", h_ctr[3],
                          kMaxSpecularIters);

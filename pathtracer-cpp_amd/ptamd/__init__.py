@@ -92,6 +92,41 @@ def _is_tensor(x) -> bool:
     return hasattr(x, "data_ptr")
 
 
+GRAD_WANT = ("rgb", "color", "emit")
+
+
+def _grad_want(want) -> Tuple[str, ...]:
+    want = tuple(want)
+    for k in want:
+        if k not in GRAD_WANT:
+            raise ValueError(f"want: {k!r} is not one of {GRAD_WANT}")
+    return want
+
+
+def _grad_io_host(num_tris: int, n: int, grad_rgb, color, emit, want):
+    """pt_trace_grad_io over numpy arrays: (io, results dict, arrays to keep alive)."""
+    want = _grad_want(want)
+    keep, res, io = [], {}, _lib.pt_trace_grad_io()
+    for key, val, rows in (("color", color, num_tris), ("emit", emit, num_tris), ("grad_rgb", grad_rgb, n)):
+        if val is None:
+            continue
+        a = np.ascontiguousarray(val, dtype=np.float32).reshape(-1)
+        if a.shape[0] != 3 * rows:
+            raise ValueError(f"{key} must hold {rows} x 3 values")
+        keep.append(a)
+        setattr(io, key, a.ctypes.data)
+    if ("color" in want or "emit" in want) and grad_rgb is None:
+        raise ValueError("grad_rgb is needed for the gradients")
+    if "rgb" in want:
+        res["rgb"] = np.empty((n, 3), dtype=np.float32)
+        io.rgb_out = res["rgb"].ctypes.data
+    for k in ("color", "emit"):
+        if k in want:
+            res[k] = np.empty((num_tris, 3), dtype=np.float64)
+            setattr(io, "grad_" + k, res[k].ctypes.data)
+    return io, res, keep
+
+
 @dataclass
 class BVH:
     """Scene container = the reference's BVH (bvh.h:30-37): triangles + built tree."""
@@ -262,6 +297,21 @@ class BVH:
                                  C.byref(st)))
         return rgb, st.as_dict()
 
+    def trace_grad(self, origins, directions, grad_rgb, depth: int, samples: int = 1, seed: int = PT_SEED, states=None,
+                   color=None, emit=None, want=GRAD_WANT):
+        """Renderer.trace_grad on the host (pt_bvh_trace_grad; no device needed): the same
+        per-path terms, summed in double in (ray, sample, bounce) order."""
+        ref = _SceneRef(self)
+        o, d = _rays(origins, directions)
+        n = o.shape[0]
+        st_arr = _states(states, n, samples)
+        prm = _lib.pt_trace_params(depth, samples, seed, st_arr.ctypes.data if st_arr is not None else None)
+        io, res, _keep = _grad_io_host(len(self.triangles), n, grad_rgb, color, emit, want)
+        st = _lib.pt_grad_stats()
+        check(lib().pt_bvh_trace_grad(C.byref(ref.s), o.ctypes.data, d.ctypes.data, n, C.byref(prm), C.byref(io),
+                                      C.byref(st)))
+        return res, st.as_dict()
+
     @classmethod
     def from_scene(cls, scene) -> "BVH":
         b = cls()
@@ -325,6 +375,7 @@ class Renderer:
         h = C.c_void_p()
         check(lib().pt_ctx_create(device, C.byref(h)))
         self.h = h
+        self.num_tris = 0  # triangles of the scene set_scene uploaded (trace_grad's override / gradient rows)
 
     def close(self) -> None:
         if getattr(self, "h", None):
@@ -358,6 +409,7 @@ class Renderer:
     def set_scene(self, bvh: BVH) -> None:
         ref = _SceneRef(bvh)
         check(lib().pt_ctx_set_scene(self.h, C.byref(ref.s)))
+        self.num_tris = len(bvh.triangles)
 
     def prepare(self) -> None:
         """Wait for the scene's background hipRTC compile (pt_ctx_prepare)."""
@@ -503,6 +555,58 @@ class Renderer:
         rgb = np.empty((n, 3), dtype=np.float32)
         check(lib().pt_ctx_trace(self.h, o.ctypes.data, d.ctypes.data, n, C.byref(prm), rgb.ctypes.data, 0, C.byref(st)))
         return rgb, st.as_dict()
+
+    def trace_grad(self, origins, directions, grad_rgb, depth: int, samples: int = 1, seed: int = PT_SEED, states=None,
+                   color=None, emit=None, want=GRAD_WANT):
+        """Radiance of trace() along the caller's rays at (optionally) changed materials, and
+        its exact gradient with respect to them (pt_ctx_trace_grad; the contract is in
+        include/pt_hip.h). `color` / `emit`: (num_tris, 3) float32 albedo / emit_color to evaluate
+        at, in the order of the BVH's triangles, None = the scene's (types and roughness always
+        the scene's; the scene itself is not changed). `grad_rgb`: (n, 3) float32 dLoss/d rgb,
+        needed for the gradients. Returns ({"rgb": (n, 3) float32, "color": (num_tris, 3)
+        float64 = dLoss/d color, "emit": likewise} restricted to `want`, stats). Rays, samples,
+        seed and states are trace()'s. numpy arrays go through host pointers; contiguous torch
+        tensors on this context's device (every array argument then) through device pointers,
+        the results are tensors there, and the inputs are left untouched."""
+        st = _lib.pt_grad_stats()
+        if _is_tensor(origins):
+            import torch
+            want = _grad_want(want)
+            n = origins.numel() // 3
+            T = self.num_tris
+            io, res = _lib.pt_trace_grad_io(), {}
+            f32 = [(origins, 3 * n), (directions, 3 * n)]
+            for key, val, cnt in (("color", color, 3 * T), ("emit", emit, 3 * T), ("grad_rgb", grad_rgb, 3 * n)):
+                if val is not None:
+                    f32.append((val, cnt))
+                    setattr(io, key, val.data_ptr())
+            for x, cnt in f32:
+                if not _is_tensor(x) or not x.is_contiguous() or not x.is_cuda or x.dtype != torch.float32 or x.numel() != cnt:
+                    raise ValueError("rays, color, emit and grad_rgb must be contiguous float32 tensors of n x 3 / "
+                                     "num_tris x 3 elements on the context's device")
+            if states is not None and (not states.is_contiguous() or not states.is_cuda or states.element_size() != 4
+                                       or states.numel() != n * samples):
+                raise ValueError("states must be a contiguous 32-bit tensor of n x samples elements on the context's device")
+            if ("color" in want or "emit" in want) and grad_rgb is None:
+                raise ValueError("grad_rgb is needed for the gradients")
+            if "rgb" in want:
+                res["rgb"] = torch.empty((n, 3), dtype=torch.float32, device=origins.device)
+                io.rgb_out = res["rgb"].data_ptr()
+            for k in ("color", "emit"):
+                if k in want:
+                    res[k] = torch.empty((T, 3), dtype=torch.float64, device=origins.device)
+                    setattr(io, "grad_" + k, res[k].data_ptr())
+            prm = _lib.pt_trace_params(depth, samples, seed, states.data_ptr() if states is not None else None)
+            check(lib().pt_ctx_trace_grad(self.h, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()), n,
+                                          C.byref(prm), C.byref(io), 1, C.byref(st)))
+            return res, st.as_dict()
+        o, d = _rays(origins, directions)
+        n = o.shape[0]
+        st_arr = _states(states, n, samples)
+        prm = _lib.pt_trace_params(depth, samples, seed, st_arr.ctypes.data if st_arr is not None else None)
+        io, res, _keep = _grad_io_host(self.num_tris, n, grad_rgb, color, emit, want)
+        check(lib().pt_ctx_trace_grad(self.h, o.ctypes.data, d.ctypes.data, n, C.byref(prm), C.byref(io), 0, C.byref(st)))
+        return res, st.as_dict()
 
     def aov(self, camera: Camera, sample: int = 0, seed: int = PT_SEED,
             channels: Sequence[str] = _lib.pt_aov.CHANNELS, part_index: int = 0, part_count: int = 1,

@@ -30,6 +30,7 @@ EXPORTED = (
     "pt_debug_scene_dark", "pt_debug_rtc_start", "pt_debug_pack_hash",
     "pt_bvh_intersect", "pt_ctx_intersect", "pt_ctx_render_aov",
     "pt_bvh_trace", "pt_ctx_trace", "pt_debug_ctx_plan", "pt_debug_walk_placement",
+    "pt_bvh_trace_grad", "pt_ctx_trace_grad",
 )
 PT_MAX_DEVICES = 16
 
@@ -105,6 +106,22 @@ class pt_trace_stats(C.Structure):
 
     def as_dict(self) -> dict:
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class pt_trace_grad_io(C.Structure):
+    """Overrides, upstream gradient and outputs of trace_grad (include/pt_hip.h); NULL = not given / not wanted."""
+    _fields_ = [("color", C.c_void_p), ("emit", C.c_void_p), ("grad_rgb", C.c_void_p), ("rgb_out", C.c_void_p),
+                ("grad_color", C.c_void_p), ("grad_emit", C.c_void_p)]
+
+
+class pt_grad_stats(C.Structure):
+    _fields_ = [("trace", pt_trace_stats), ("terms", C.c_uint64), ("grad_ms", C.c_double), ("lds_table", C.c_int32),
+                ("reserved", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        d = self.trace.as_dict()
+        d.update(terms=self.terms, grad_ms=self.grad_ms, lds_table=self.lds_table)
+        return d
 
 
 class pt_aov(C.Structure):
@@ -207,6 +224,11 @@ def lib() -> C.CDLL:
         L.pt_bvh_trace.argtypes = [C.POINTER(pt_scene), P, P, C.c_int64, C.POINTER(pt_trace_params), P,
                                    C.POINTER(pt_trace_stats)]
         L.pt_ctx_trace.argtypes = [P, P, P, C.c_int64, C.POINTER(pt_trace_params), P, C.c_int, C.POINTER(pt_trace_stats)]
+        if hasattr(L, "pt_ctx_trace_grad"):  # absent from older builds used in A/B runs
+            L.pt_bvh_trace_grad.argtypes = [C.POINTER(pt_scene), P, P, C.c_int64, C.POINTER(pt_trace_params),
+                                            C.POINTER(pt_trace_grad_io), C.POINTER(pt_grad_stats)]
+            L.pt_ctx_trace_grad.argtypes = [P, P, P, C.c_int64, C.POINTER(pt_trace_params), C.POINTER(pt_trace_grad_io),
+                                            C.c_int, C.POINTER(pt_grad_stats)]
         if hasattr(L, "pt_debug_rccl_failover"):  # test hooks (absent from older builds used in A/B runs)
             L.pt_debug_rccl_failover.argtypes = [C.c_int32, C.c_int32, P]
         if hasattr(L, "pt_debug_rtc_cache"):

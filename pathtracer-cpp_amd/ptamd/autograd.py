@@ -1,0 +1,59 @@
+"""trace() along fixed rays as a differentiable function of the scene's colours and emissions.
+
+`trace_radiance(renderer, origins, directions, color, emit, depth, samples, seed)` returns the
+radiance `Renderer.trace` would give on a scene whose triangles carry `color` / `emit`, and its
+backward pass returns the exact gradients with respect to both (Renderer.trace_grad: the paths do
+not depend on either, so the radiance is a polynomial in them). torch is imported on first use.
+"""
+from __future__ import annotations
+
+_fn = None
+
+
+def _function():
+    global _fn
+    if _fn is not None:
+        return _fn
+    import torch
+
+    class TraceRadiance(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, renderer, origins, directions, color, emit, depth, samples, seed, states):
+            c = None if color is None else color.detach().to(torch.float32).contiguous()
+            e = None if emit is None else emit.detach().to(torch.float32).contiguous()
+            res, _ = renderer.trace_grad(origins, directions, None, depth, samples=samples, seed=seed, states=states,
+                                         color=c, emit=e, want=("rgb",))
+            ctx.renderer, ctx.rays, ctx.mats = renderer, (origins, directions, states), (c, e)
+            ctx.args = (depth, samples, seed)
+            ctx.dtypes = (None if color is None else color.dtype, None if emit is None else emit.dtype)
+            return res["rgb"]
+
+        @staticmethod
+        def backward(ctx, grad_rgb):
+            origins, directions, states = ctx.rays
+            c, e = ctx.mats
+            depth, samples, seed = ctx.args
+            need_c = c is not None and ctx.needs_input_grad[3]
+            need_e = e is not None and ctx.needs_input_grad[4]
+            want = tuple(k for k, need in (("color", need_c), ("emit", need_e)) if need)
+            g_c = g_e = None
+            if want:
+                g = grad_rgb.detach().to(torch.float32).contiguous()
+                res, _ = ctx.renderer.trace_grad(origins, directions, g, depth, samples=samples, seed=seed, states=states,
+                                                 color=c, emit=e, want=want)
+                if need_c:
+                    g_c = res["color"].to(ctx.dtypes[0])
+                if need_e:
+                    g_e = res["emit"].to(ctx.dtypes[1])
+            return None, None, None, g_c, g_e, None, None, None, None
+
+    _fn = TraceRadiance
+    return _fn
+
+
+def trace_radiance(renderer, origins, directions, color, emit, depth, samples=1, seed=1, states=None):
+    """rgb (n, 3) float32 on the rays' device: trace() along the rays at the given `color` and
+    `emit` ((num_tris, 3) tensors on the renderer's device, either may be None = the scene's),
+    differentiable with respect to both. origins, directions (and states) are contiguous float32
+    (32-bit integer) tensors on that device, as for Renderer.trace_grad."""
+    return _function().apply(renderer, origins, directions, color, emit, depth, samples, seed, states)

@@ -20,6 +20,13 @@ sample the two images are compared bit for bit before anything is timed (with 16
 jitters a camera ray per sample, the trace repeats sample 0's). Mray/s = traced segments / kernel
 time (trace: the path kernel alone; its in-order sum pass is reported beside it). Writes
 <out>/<scene>.json (default profiles/paths).
+
+--mode grad: pt_ctx_trace_grad (rgb and both gradients, device buffers, a seeded grad_rgb) beside
+pt_ctx_trace on the same ray set, states, depth and samples as --mode trace, timed in turn on the
+same visit. Mray/s = traced segments / the path kernel's time; the table form that ran is
+reported, and where it is the per-block LDS table the global-atomics form (PT_GRAD_LDS=0) is timed
+too, with its atomic bytes per second (8 B per non-zero channel added). The forward values are
+compared bit for bit before anything is timed. Writes <out>/<scene>.json (default profiles/grad).
 """
 import argparse
 import json
@@ -192,6 +199,70 @@ def bench_trace_scene(name, res, min_ms, warmup, depth=5):
             "min_kernel_ms": min_ms, "device": torch.cuda.get_device_name(0), "lines": lines}
 
 
+def bench_grad_scene(name, res, min_ms, warmup, depth=5):
+    import torch
+    import ptamd
+    from ptamd import scenes
+    sc = scenes.cornell((res, res)) if name == "cornell" else scenes.sphere_in_cornell(int(name[len("sphere"):]), (res, res))
+    bvh = ptamd.BVH.from_scene(sc)
+    cam = ptamd.Camera.from_spec(sc.camera)
+    r = ptamd.Renderer(0)
+    r.set_scene(bvh)
+    r.prepare()
+    aov, _ = r.aov(cam, sample=0, channels=("ray",))
+    rays = aov["ray"].reshape(-1, 6)
+    n = rays.shape[0]
+    dev = torch.device("cuda", 0)
+    to = torch.from_numpy(np.ascontiguousarray(rays[:, 0:3])).to(dev)
+    td = torch.from_numpy(np.ascontiguousarray(rays[:, 3:6])).to(dev)
+    tg = torch.from_numpy(np.random.default_rng(5).uniform(-1, 1, (n, 3)).astype(np.float32)).to(dev)
+    out = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    lines = {}
+    forms = {}
+    for spp in (1, 16):
+        states = torch.from_numpy(camera_states(n, spp, ptamd.PT_SEED).view(np.int32)).to(dev)
+        info = {}
+
+        def trace_call():
+            _, st = r.trace(to, td, depth, samples=spp, states=states, out=out)
+            info["trace"] = st
+            return st["rays"], st["kernel_ms"]
+
+        def grad_call(global_form=False):
+            if global_form:
+                os.environ["PT_GRAD_LDS"] = "0"
+            try:
+                res_, st = r.trace_grad(to, td, tg, depth, samples=spp, states=states)
+            finally:
+                os.environ.pop("PT_GRAD_LDS", None)
+            info["grad"], info["res"] = st, res_
+            return st["rays"], st["kernel_ms"]
+
+        t_rays, _ = trace_call()
+        g_rays, _ = grad_call()
+        assert t_rays == g_rays and torch.equal(out.view(torch.int32), info["res"]["rgb"].view(torch.int32)), \
+            f"{name}: trace and trace_grad forward values differ"
+        nonzero = int((info["res"]["color"] != 0).sum() + (info["res"]["emit"] != 0).sum())
+        lds = info["grad"]["lds_table"]
+        forms[f"spp{spp}"] = "lds" if lds else "global"
+        todo = [("trace", trace_call), ("grad", grad_call)] + ([("grad_global", lambda: grad_call(True))] if lds else [])
+        for label, call in todo:
+            key = f"{label}_spp{spp}"
+            lines[key] = timed(call, warmup, min_ms)
+            if label != "trace":
+                st = info["grad"]
+                lines[key].update(terms_per_call=st["terms"], grad_ms_per_call=st["grad_ms"], lds_table=st["lds_table"],
+                                  sum_pass_ms_per_call=st["reduce_ms"], call_total_ms=st["total_ms"],
+                                  nonzero_outputs=nonzero)
+                lines[key]["ratio_to_trace"] = lines[key]["mrays_per_s"] / lines[f"trace_spp{spp}"]["mrays_per_s"]
+                # an upper bound of the atomic bytes: 3 channels x 8 B per term (zero channels are skipped)
+                lines[key]["term_gbytes_per_s"] = st["terms"] * 24 * lines[key]["calls"] / lines[key]["kernel_ms"] / 1e6
+    placement = {k: info["grad"][k] for k in ("lds_scene", "lds_stack", "lds_records")}
+    r.close()
+    return {"scene": sc.name, "tris": len(sc.tris), "res": [res, res], "rays": n, "depth": depth, "placement": placement,
+            "table_form": forms, "min_kernel_ms": min_ms, "device": torch.cuda.get_device_name(0), "lines": lines}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--scenes", default="cornell,sphere223")
@@ -199,17 +270,21 @@ def main():
     ap.add_argument("--min-ms", type=float, default=1000.0, help="kernel time per line")
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--mode", choices=("query", "trace"), default="query")
-    ap.add_argument("--out", default=None, help="default profiles/query, or profiles/paths with --mode trace")
+    ap.add_argument("--mode", choices=("query", "trace", "grad"), default="query")
+    ap.add_argument("--out", default=None, help="default profiles/query, profiles/paths with --mode trace, profiles/grad with --mode grad")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "paths" if args.mode == "trace" else "query")
-    if args.mode == "trace":
-        os.environ["PT_TEST_HOOKS"] = "1"  # PT_FLAT / PT_WIDE pick the yardstick's kernel
+        args.out = os.path.join(ROOT, "profiles", {"trace": "paths", "grad": "grad"}.get(args.mode, "query"))
+    if args.mode in ("trace", "grad"):
+        os.environ["PT_TEST_HOOKS"] = "1"  # PT_FLAT / PT_WIDE pick the yardstick's kernel, PT_GRAD_LDS the table form
     os.makedirs(args.out, exist_ok=True)
     for name in args.scenes.split(","):
-        res = bench_trace_scene(name, args.res, args.min_ms, args.warmup) if args.mode == "trace" else \
-            bench_scene(name, args.res, args.min_ms, args.warmup, args.seed)
+        if args.mode == "grad":
+            res = bench_grad_scene(name, args.res, args.min_ms, args.warmup)
+        elif args.mode == "trace":
+            res = bench_trace_scene(name, args.res, args.min_ms, args.warmup)
+        else:
+            res = bench_scene(name, args.res, args.min_ms, args.warmup, args.seed)
         with open(os.path.join(args.out, res["scene"] + ".json"), "w") as f:
             json.dump(res, f, indent=1)
             f.write("\n")
