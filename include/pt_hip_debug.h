@@ -88,6 +88,20 @@ int pt_debug_walk_placement(int32_t num_nodes, int32_t num_tris, int32_t tree_de
  * triangle: emission +0, finite albedo, a unit-length shading normal, SPECULAR roughness
  * |r| <= 1.15 so that cos theta is finite; pt_launch.hip scene_dark), 0 if not, < 0 on error. */
 int pt_debug_scene_dark(const pt_scene* scene);
+/* Test hook, no device needed: the last-ray rule's predicate (emit_reject, pt_math.h) on n
+ * rays: box6[6i..] = {E lb.xyz, E rt.xyz}, org / dir 3 floats each -> out[i] = 1 if ray i provably
+ * fails the reference's slab test for every box inside E. */
+int pt_debug_emit_reject(const float* box6, const float* org, const float* dir, int64_t n, uint8_t* out);
+/* Test hook, no device needed: the emitter box the host computes for `scene` (the union of the
+ * tree's leaf boxes that hold an EMIT triangle; lb = +inf, rt = -inf when there is none, which
+ * rejects every last ray). Returns 1 if the rule is on (a dark scene, PT_EMIT_REJECT not 0), 0 if
+ * off (out is then all zero), < 0 on error. */
+int pt_debug_emit_box(const pt_scene* scene, float out[6]);
+/* Test hook: the same for a context's scene (*on, box[6]), and *early = the paths the rule ended
+ * in the context's last render. Counted only by kernels built with PT_COUNT_EARLY=1: the offline
+ * render kernels are, the hipRTC scene kernel under PT_RTC_DEFINES=PT_COUNT_EARLY=1 (else 0).
+ * Any pointer may be NULL. */
+int pt_debug_ctx_emit_reject(const pt_ctx* ctx, int32_t* on, float box[6], uint64_t* early);
 /* Test hook: process-wide counters. which = 0: contexts created (pt_ctx_create), 1: scene
  * uploads (pt_ctx_set_scene), 2: cached multi-device context sets live, 3: uploads skipped
  * because a cached context already held the same scene. */

@@ -124,6 +124,13 @@ struct PackedScene {
     bool coords_small = false;  // every vertex coordinate below 2^60 in magnitude (tri_hit_nb's precondition)
 };
 
+// The last-ray rule's emitter box (scene_emit_box in pt_launch.h): the union
+// of the tree's leaf boxes that hold an EMIT triangle; lo = +inf, hi = -inf when there is none.
+struct EmitBox {
+    bool on = false;  // the rule applies (a dark scene; PT_EMIT_REJECT=0 turns it off)
+    float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+};
+
 // Validate the node graph and pack it. Returns PT_OK or an error code.
 int pack_scene(const pt_scene* s, PackedScene& out);
 

@@ -276,6 +276,8 @@ struct pt_ctx {
     bool has_specular = false;  // the scene holds a SPECULAR material
     bool albedo_x2 = false;     // the scene kernel unwinds with pre-doubled albedo (albedo_x2_ok)
     bool dark = false;          // every bounce material is dark (scene_dark): finish_path's skip
+    EmitBox emit;               // the last-ray rule and its emitter box (scene_emit_box)
+    uint64_t last_early = 0;    // paths the rule ended in the last render (PT_COUNT_EARLY kernels; ctr[4])
     void* flat_fast = nullptr;  // the flat table kernel with the scene's flags (pt_flat_fast.hip), or none
     int flat_boxes = 0;         // box-level pairs in the hipRTC kernel: distinct boxes (its LDS table), else 0
     bool rtc_requested = false; // a hipRTC scene kernel was requested for the scene
@@ -782,6 +784,9 @@ int fill_trace_args(pt_ctx* c, const RenderPlan& P, const pt_camera* cam, const 
     A.work = c->d_ctr;
     A.ctr = c->d_ctr;
     A.dark = c->dark ? 1 : 0;
+    A.emit_on = c->emit.on ? 1 : 0;
+    A.emit_lo_x = c->emit.lo[0], A.emit_lo_y = c->emit.lo[1], A.emit_lo_z = c->emit.lo[2];
+    A.emit_hi_x = c->emit.hi[0], A.emit_hi_y = c->emit.hi[1], A.emit_hi_z = c->emit.hi[2];
     fill_camera(A, cam, P.shape, prm);
     A.depth = prm->depth;
     A.per_item = P.per_item;
@@ -964,8 +969,9 @@ void report_stamps(const pt_ctx* c, bool wide, const unsigned long long* h_ctr) 
                 100 * hs[1] / tot, 100 * hs[2] / tot, 100 * hs[3] / tot, 100 * hs[4] / tot);
         const double it = (double)(hs[7] ? hs[7] : 1);
         if (!wide)
-            fprintf(stderr, "[stamps] per flat wave-iteration: pairs %.1f, pair rounds %.2f, max pairs of a lane %.2f\n",
-                hs[8] / it, hs[9] / it, hs[10] / it);
+            fprintf(stderr, "[stamps] per flat wave-iteration: pairs %.1f, pair rounds %.2f, max pairs of a lane %.2f, "
+                    "rays credited %.2f (%llu wave-iterations)\n",
+                hs[8] / it, hs[9] / it, hs[10] / it, (double)h_ctr[1] / it, hs[7]);
     }
 }
 #endif
@@ -1002,7 +1008,7 @@ int finish_render(pt_ctx* c, const RenderPlan& P, const TraceArgs& A, const pt_p
         }
         if (launches == 0) prm->progress(prm->progress_user, total, total);
     }
-    unsigned long long h_ctr[4] = {0, 0, 0, 0};
+    unsigned long long h_ctr[5] = {0, 0, 0, 0, 0};
     hipError_t e = hipMemcpyAsync(h_ctr, c->d_ctr, sizeof(h_ctr), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess && !out_is_device)
         e = hipMemcpyAsync(out, dst, 3 * (size_t)npix * sizeof(float), hipMemcpyDeviceToHost, c->stream);
@@ -1026,6 +1032,7 @@ int finish_render(pt_ctx* c, const RenderPlan& P, const TraceArgs& A, const pt_p
                               P.batch, P.per_item, P.fused, P.tail, P.flagged ? P.flags_pm : -1, launches, A.regen_thresh,
                               A.theta_lanes, log.grid, log.chunk, (int64_t)log.static_items, log.acc_every, c->num_cus};
     memcpy(c->last_plan, plan, sizeof(plan));
+    c->last_early = h_ctr[4];
     if (stats) {
         stats->rays = h_ctr[1];
         stats->paths = (uint64_t)(P.spp - P.s_lo) * (uint64_t)npix;
@@ -1064,7 +1071,7 @@ int render_range(pt_ctx* c, const pt_camera* cam, const pt_params* prm, int s_lo
     TraceArgs A;
     if ((rc = fill_trace_args(c, P, cam, prm, A))) return rc;
 
-    HIP_TRY(hipMemsetAsync(c->d_ctr, 0, 4 * sizeof(unsigned long long), c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_ctr, 0, 5 * sizeof(unsigned long long), c->stream));
 #ifdef PT_STAMPS
     if (!c->d_stamps) HIP_TRY(hipMalloc((void**)&c->d_stamps, kStampSections * sizeof(unsigned long long)));
     HIP_TRY(hipMemsetAsync(c->d_stamps, 0, kStampSections * sizeof(unsigned long long), c->stream));
@@ -1133,7 +1140,7 @@ int pt_ctx_create(int device, pt_ctx** out) {
         if (hipSetDevice(c->device) != hipSuccess) c->init_error = "hipSetDevice failed";
         else if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess)
             c->init_error = "stream creation failed";
-        else if (hipMalloc((void**)&c->d_ctr, 4 * sizeof(unsigned long long)) != hipSuccess)
+        else if (hipMalloc((void**)&c->d_ctr, 5 * sizeof(unsigned long long)) != hipSuccess)
             c->init_error = "counter allocation failed";
     };
     // PT_CTX_SYNC=1 (test hook): made here, as before round 6
@@ -1193,13 +1200,14 @@ int pt_ctx_set_scene(pt_ctx* c, const pt_scene* scene) {
     const bool specular = scene_has_specular(ps);
     const bool albedo_x2 = albedo_x2_ok(ps);
     const bool dark = scene_dark(ps);
+    const EmitBox emit = scene_emit_box(ps, dark);
     // The scene-specialised kernel's compile starts before the upload (and before the
     // context's stream is waited for): renders pick it up (render_range: rtc_resolve).
     const bool want_rtc = flat_eligible(ps) && !hook_off("PT_RTC");
     std::string src;
     RtcFuture job;
     if (want_rtc) {
-        src = rtc_flat_source(ps.leaves, ps.num_leaves, specular, ps.coords_small, albedo_x2, dark);
+        src = rtc_flat_source(ps.leaves, ps.num_leaves, specular, ps.coords_small, albedo_x2, dark, emit);
         job = rtc_job(src);
     }
     if ((rc = ctx_ready(c))) return rc;
@@ -1254,6 +1262,7 @@ int pt_ctx_set_scene(pt_ctx* c, const pt_scene* scene) {
     ps.rank_tri.clear();
     c->has_specular = specular;
     c->dark = dark;
+    c->emit = emit;
     c->albedo_x2 = false;
     // the table kernel a flat scene runs until its hipRTC kernel is ready: with the scene's
     // flags when it has the usual ones (PT_FLAT_FAST=0, test hook: the fully generic one)
@@ -1965,6 +1974,37 @@ int pt_debug_ctx_flags(const pt_ctx* c, int32_t out[5]) {
     out[2] = c->rtc_requested ? 1 : 0;
     out[3] = c->meta.num_wide;
     out[4] = c->dark ? 1 : 0;
+    return PT_OK;
+}
+
+// Test hook: the last-ray rule of the context's scene and its count in the last render (pt_hip_debug.h).
+int pt_debug_ctx_emit_reject(const pt_ctx* c, int32_t* on, float box[6], uint64_t* early) {
+    if (!c) return set_error(PT_E_ARG, "pt_debug_ctx_emit_reject: NULL argument");
+    if (on) *on = c->emit.on ? 1 : 0;
+    if (box)
+        for (int a = 0; a < 3; a++) box[a] = c->emit.lo[a], box[3 + a] = c->emit.hi[a];
+    if (early) *early = c->last_early;
+    return PT_OK;
+}
+
+// Test hook (no device needed): the last-ray rule's emitter box of a scene (scene_emit_box).
+int pt_debug_emit_box(const pt_scene* scene, float out[6]) {
+    if (!out) return set_error(PT_E_ARG, "pt_debug_emit_box: NULL argument");
+    PackedScene ps;
+    const int rc = pack_scene(scene, ps);
+    if (rc) return rc;
+    const EmitBox e = scene_emit_box(ps, scene_dark(ps));
+    for (int a = 0; a < 3; a++) out[a] = e.lo[a], out[3 + a] = e.hi[a];
+    return e.on ? 1 : 0;
+}
+
+// Test hook (no device needed): emit_reject (pt_math.h) on n rays against n boxes.
+int pt_debug_emit_reject(const float* box6, const float* org, const float* dir, int64_t n, uint8_t* out) {
+    if (!box6 || !org || !dir || !out || n < 0) return set_error(PT_E_ARG, "pt_debug_emit_reject: bad argument");
+    for (int64_t i = 0; i < n; i++) {
+        const float *b = box6 + 6 * i, *o = org + 3 * i, *d = dir + 3 * i;
+        out[i] = emit_reject(v3{b[0], b[1], b[2]}, v3{b[3], b[4], b[5]}, v3{o[0], o[1], o[2]}, v3{d[0], d[1], d[2]}) ? 1 : 0;
+    }
     return PT_OK;
 }
 

@@ -94,6 +94,9 @@ bool flat_eligible(const PackedScene& m);
 bool scene_has_specular(const PackedScene& ps);  // a SPECULAR material: the sampler is compiled in
 bool scene_dark(const PackedScene& ps);          // finish_path may skip paths that end at +0 (§3.9)
 bool albedo_x2_ok(const PackedScene& ps);        // the flat kernel may unwind with pre-doubled albedo
+// The last-ray rule (§3.15): on in a dark scene (`dark`: scene_dark), with the union of the leaf
+// boxes that hold an EMIT triangle. Test hook PT_EMIT_REJECT=0 turns it off.
+EmitBox scene_emit_box(const PackedScene& ps, bool dark);
 
 // ---- the binary walk of pt_query.hip and pt_paths.hip.
 // Where a launch keeps the scene, the walk's stack and the path records, and its grid.

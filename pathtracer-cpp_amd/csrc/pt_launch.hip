@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <limits>
 
 #include "pt_launch.h"
 #include "pt_trace.h"
@@ -244,6 +245,43 @@ bool scene_dark(const PackedScene& ps) {
         if (!(n2 >= 0.999 && n2 <= 1.001)) return false;
     }
     return true;
+}
+
+// The last-ray rule's box (shade, pt_trace.h; the proof is with emit_reject, pt_math.h): the union
+// E of the leaf boxes of every leaf that holds an EMIT triangle. The boxes are the binary
+// tree's leaf nodes, which are the boxes every kernel form and the reference test before a
+// triangle: the flat list copies them (pack_scene), the wide tree stores them with its
+// triangles (or forms the same box from a single triangle's vertices), and a caller-built
+// tree's leaf box may be larger than its triangles. An ancestor's box failing only removes
+// more tests, so a ray that fails every emitter leaf box tests no emitter triangle.
+// Only dark scenes (scene_dark): the last segment then returns +0 for anything but an emitter
+// and the levels above it unwind +0 to +0. Emitters may have any emission. A NaN in an
+// emitter leaf's box (the proof orders the planes) turns the rule off.
+EmitBox scene_emit_box(const PackedScene& ps, bool dark) {
+    EmitBox e;
+    if (!dark || hook_off("PT_EMIT_REJECT")) return e;
+    for (int a = 0; a < 3; a++) {
+        e.lo[a] = std::numeric_limits<float>::infinity();
+        e.hi[a] = -std::numeric_limits<float>::infinity();
+    }
+    const size_t ntri = ps.mats.size() / 2;
+    for (size_t n = 0; 2 * n + 1 < ps.nodes.size(); n++) {
+        const f4 p = ps.nodes[2 * n], q = ps.nodes[2 * n + 1];
+        const int a = __builtin_bit_cast(int, q.z), b = __builtin_bit_cast(int, q.w);
+        if (a >= 0) continue;  // interior
+        bool emits = false;
+        for (int i = -a - 1; i <= b && i >= 0 && (size_t)i < ntri; i++)
+            if (__builtin_bit_cast(int, ps.mats[2 * (size_t)i].x) == PT_MAT_EMIT) emits = true;
+        if (!emits) continue;
+        const float lb[3] = {p.x, p.y, p.z}, rt[3] = {p.w, q.x, q.y};
+        for (int ax = 0; ax < 3; ax++) {
+            if (!(lb[ax] <= rt[ax])) return EmitBox();  // NaN or an inverted box: no claim
+            e.lo[ax] = std::min(e.lo[ax], lb[ax]);
+            e.hi[ax] = std::max(e.hi[ax], rt[ax]);
+        }
+    }
+    e.on = true;
+    return e;
 }
 
 // Whether the flat kernel may unwind with pre-doubled albedo (finish_path<., true>: L * 2a

@@ -175,6 +175,43 @@ PT_HD bool all_finite(v3 a) {
            __builtin_fabsf(a.z) < __builtin_inff();
 }
 
+// Whether ray (o, d) provably fails slab_hit (aabb.h:20-29, inv = 1 / d) for EVERY box
+// [lb, rt] inside E = [elb, ert] (elb <= lb <= rt <= ert per axis, no NaN in the boxes):
+// on some axis a the origin lies outside E and the direction points away from it,
+//     o.a < elb.a and -2 < d.a < 0,   or   o.a > ert.a and 0 < d.a < 2.
+// The render kernels use it with E = the union of the leaf boxes that hold an EMIT
+// triangle: a rejected ray tests no emitter triangle.
+// Proof for the first case (the second mirrors it: both differences are negative, inv.a > 0).
+//   * The differences are non-zero: lb.a >= elb.a > o.a and rt.a >= lb.a, so lb.a - o.a
+//     and rt.a - o.a are positive reals, and a float subtraction of unequal operands never
+//     rounds to zero (denormals are kept); it may round to +inf, which is positive too.
+//   * The products do not underflow: inv.a = 1 / d.a is negative with |inv.a| > 1/2
+//     (-inf when d.a is a small subnormal). A non-zero x times such a factor has magnitude
+//     above 2^-150, which rounds to 2^-149 or more, never to -0 (the only reason for the
+//     bound on |d.a|: -0 would pass `tmax < 0`). So t1.a and t2.a are strictly negative
+//     (or -inf), neither is NaN, and M_a = max(t1.a, t2.a) < 0.
+//   * tmax = std_min3(M_x, M_y, M_z) is a left fold with `<` (std::min of an initializer
+//     list). a = x: r starts at M_x < 0 and a later NaN never replaces it (`NaN < r` is
+//     false), so tmax <= M_x < 0. a = y: r is M_x; if it is NaN (0 * inf) then `M_y < r` and
+//     `M_z < r` are false and tmax is NaN, else r becomes min(M_x, M_y) <= M_y < 0 and stays
+//     negative. a = z: r after two steps is NaN (then tmax is NaN) or a number, and the last
+//     step gives min(r, M_z) <= M_z < 0. So tmax < 0, which fails `!(tmax < 0)`, or tmax is
+//     NaN, which fails `tmin <= tmax`.
+//   * NaN in o or d: every comparison below is false, the ray is not rejected. d.a = +-0
+//     satisfies neither d.a < 0 nor d.a > 0.
+//   * E empty (elb = +inf, ert = -inf: no box to hit): every ray with a non-zero component
+//     of magnitude below 2 is rejected, vacuously right.
+// The rule never claims a hit; a ray that is not rejected is traced as before.
+// Bitwise & and | on purpose: 15 compares and mask operations in a straight line. The
+// short-circuit forms compiled to a dozen divergent branches in the kernels' shade section.
+PT_HD int emit_reject_axis(float lo, float hi, float o, float d) {
+    return (int)(__builtin_fabsf(d) < 2.0f) & (((int)(o < lo) & (int)(d < 0.0f)) | ((int)(o > hi) & (int)(d > 0.0f)));
+}
+PT_HD bool emit_reject(v3 elb, v3 ert, v3 o, v3 d) {
+    return (emit_reject_axis(elb.x, ert.x, o.x, d.x) | emit_reject_axis(elb.y, ert.y, o.y, d.y) |
+            emit_reject_axis(elb.z, ert.z, o.z, d.z)) != 0;
+}
+
 // ------------------------------------------------------------------ Möller–Trumbore (triangle.h:25-44)
 // e1 = v2 - v1 and e2 = v3 - v1 are precomputed on the host with the same float ops.
 PT_HD bool tri_hit(v3 v1, v3 e1, v3 e2, v3 o, v3 d, float& t) {

@@ -30,8 +30,9 @@ int flat_box_pairs(const std::vector<f4>& leaves, int n, std::vector<uint16_t>* 
 bool leaves_single(const std::vector<f4>& leaves, int n);
 // The scene kernel's source for a flat leaf list and the scene's flags (scene_has_specular,
 // PackedScene::coords_small, albedo_x2_ok, scene_dark: pt_launch.h).
+// `emit`: the last-ray rule's box (scene_emit_box), baked in as literals when it is on.
 std::string rtc_flat_source(const std::vector<f4>& leaves, int n, bool specular, bool tri_fast, bool albedo_x2,
-                            bool dark);
+                            bool dark, const EmitBox& emit);
 // The compile job for `src`, shared by every context and device that asks for the same source.
 RtcFuture rtc_job(const std::string& src);
 // Whether compiles can run in the background (else rtc_job's compile runs on first get()).

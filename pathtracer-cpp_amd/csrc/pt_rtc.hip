@@ -24,6 +24,7 @@
 #include <chrono>
 #include <fstream>
 #include <future>
+#include <limits>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -54,6 +55,13 @@ std::string hexf(float v) {
     char b[64];
     snprintf(b, sizeof(b), "%af", (double)v);
     return b;
+}
+
+// hexf, and an infinity spelled so that it compiles (the empty emitter box).
+std::string litf(float v) {
+    if (v == std::numeric_limits<float>::infinity()) return "__builtin_inff()";
+    if (v == -std::numeric_limits<float>::infinity()) return "-__builtin_inff()";
+    return hexf(v);
 }
 
 }  // namespace
@@ -106,7 +114,7 @@ namespace {
 // plane (c - o) * inv is computed once, boxes shared by several leaves are tested once,
 // and a flat axis (lb == rt) needs no min/max. Same IEEE operations as slab_hit_finite.
 std::string flat_mask_source(const std::vector<f4>& leaves, int n, bool specular, bool tri_fast, bool albedo_x2,
-                             bool dark) {
+                             bool dark, const EmitBox& emit) {
     std::vector<std::map<uint32_t, int>> planes(3);
     auto plane = [&](int ax, float c) {
         auto it = planes[ax].find(f2u(c));
@@ -269,6 +277,16 @@ std::string flat_mask_source(const std::vector<f4>& leaves, int n, bool specular
     std::string tabs = "{";
     for (size_t u = 0; u < box_tab.size(); u++) tabs += (u ? ", " : "") + std::to_string(box_tab[u]) + "u";
     tabs += box_tab.empty() ? "0u}" : "}";
+    // the last-ray rule (shade): the emitter box as literals, so the kernel compares against
+    // constants and holds no registers for it; off: the rule is not compiled in
+    std::string rej = "    using EmitRej = NoEmitReject;\n";
+    if (emit.on)
+        rej = "    struct EmitRej {\n        static constexpr bool kCompiled = true;\n"
+              "        __device__ __forceinline__ static bool on() { return true; }\n"
+              "        __device__ __forceinline__ static bool rejected(v3 o, v3 d) {\n"
+              "            return emit_reject(v3{" + litf(emit.lo[0]) + ", " + litf(emit.lo[1]) + ", " + litf(emit.lo[2]) +
+              "}, v3{" + litf(emit.hi[0]) + ", " + litf(emit.hi[1]) + ", " + litf(emit.hi[2]) + "}, o, d);\n"
+              "        }\n    };\n";
     return std::string("#ifndef PT_FLAT_SIGN_MASK\n#define PT_FLAT_SIGN_MASK 0\n#endif\n#define KSIGN (PT_FLAT_SIGN_MASK && ") +
            (sign ? "1" : "0") + ")\n" + "#define KBOX " + (nbox > 0 ? "(!KSIGN)" : "0") + "\n" +
            "namespace pt {\nstruct SceneBoxMask {\n    static constexpr bool kSignMask = KSIGN;\n"
@@ -280,7 +298,7 @@ std::string flat_mask_source(const std::vector<f4>& leaves, int n, bool specular
            ";\n    static constexpr bool kTriFast = " + (tri_fast ? "true" : "false") +
            ";\n    static constexpr bool kAlbedoX2 = " + (albedo_x2 ? "true" : "false") +
            ";\n    static constexpr bool kDarkKnown = true;\n    static constexpr bool kDark = " + (dark ? "true" : "false") +
-           ";\n    __device__ __forceinline__ static unsigned long long "
+           ";\n" + rej + "    __device__ __forceinline__ static unsigned long long "
            "mask(const TraceArgs&, v3 o, v3 inv) {\n" +
            body + tests + acc + "        return m;\n    }\n};\n}  // namespace pt\n";
 }
@@ -336,7 +354,7 @@ std::vector<std::string> rtc_extra_flags() {
 }  // namespace
 
 std::string rtc_flat_source(const std::vector<f4>& leaves, int n, bool specular, bool tri_fast, bool albedo_x2,
-                            bool dark) {
+                            bool dark, const EmitBox& emit) {
     std::string fl = "// extra flags:";
     for (const std::string& f : rtc_extra_flags()) fl += " " + f;
     // camera fields from the kernel's argument registers at 8 waves: +0.5-1.0 % on configs
@@ -352,7 +370,7 @@ std::string rtc_flat_source(const std::vector<f4>& leaves, int n, bool specular,
            "typedef __hip_internal::uint8_t uint8_t; typedef __hip_internal::uint16_t uint16_t;\n"
            "#if !defined(__HIP_DEVICE_COMPILE__)\n#error expected a device compilation (pt_math.h fast paths)\n#endif\n"
            "#include \"pt_trace.h\"\n" +
-           flat_mask_source(leaves, n, specular, tri_fast, albedo_x2, dark) +
+           flat_mask_source(leaves, n, specular, tri_fast, albedo_x2, dark, emit) +
            "extern \"C\" __global__ __launch_bounds__(256, PT_WAVES) void pt_trace_flat_rtc(pt::TraceArgs A) {\n"
            "    pt::trace_body_flat<pt::SceneBoxMask>(A);\n}\n";
 }
@@ -855,7 +873,8 @@ int pt_rtc_check(const pt_scene* scene, char* src_out, size_t cap) {
     if (!flat_eligible(ps))
         return set_error(PT_E_ARG, "scene has no flat leaf list (%d leaves, %d triangles)", ps.num_leaves, ps.num_tris);
     const std::string src =
-        rtc_flat_source(ps.leaves, ps.num_leaves, scene_has_specular(ps), ps.coords_small, albedo_x2_ok(ps), scene_dark(ps));
+        rtc_flat_source(ps.leaves, ps.num_leaves, scene_has_specular(ps), ps.coords_small, albedo_x2_ok(ps), scene_dark(ps),
+                        scene_emit_box(ps, scene_dark(ps)));
     if (src_out && cap) {
         const size_t n = std::min(cap - 1, src.size());
         memcpy(src_out, src.data(), n);
@@ -876,7 +895,8 @@ int pt_debug_rtc_start(const pt_scene* scene) {
     if (!flat_eligible(ps))
         return set_error(PT_E_ARG, "scene has no flat leaf list (%d leaves, %d triangles)", ps.num_leaves, ps.num_tris);
     const RtcFuture f = rtc_job(
-        rtc_flat_source(ps.leaves, ps.num_leaves, scene_has_specular(ps), ps.coords_small, albedo_x2_ok(ps), scene_dark(ps)));
+        rtc_flat_source(ps.leaves, ps.num_leaves, scene_has_specular(ps), ps.coords_small, albedo_x2_ok(ps), scene_dark(ps),
+                        scene_emit_box(ps, scene_dark(ps))));
     return f.wait_for(std::chrono::seconds(0)) == std::future_status::ready ? 0 : 1;
 }
 

@@ -214,7 +214,8 @@ struct TraceArgs {
     const float4* __restrict__ nrm;        // wide: {n.xyz, material id} per rank position
     const float4* __restrict__ umats;      // wide: distinct materials (2 float4 each)
     float* __restrict__ radiance;          // [s_count][npix][3]
-    unsigned long long* __restrict__ ctr;  // [0] work head, [1] rays, [2] (unused), [3] runaway
+    unsigned long long* __restrict__ ctr;  // [0] work head, [1] rays, [2] chunk head (fused sums), [3] runaway,
+                                           // [4] paths the last-ray rule ended (PT_COUNT_EARLY builds; renders only)
     unsigned long long* __restrict__ work; // the work head (ctr + 0)
     unsigned long long* stamps;            // PT_STAMPS builds: kStampSections cycle sums
     unsigned long long total_items;
@@ -264,6 +265,12 @@ struct TraceArgs {
     const float2* __restrict__ theta_tab;  // PT_THETA_TAB: (sin, cos) of theta per grid x (hemisphere_dir_tab)
     int theta_lanes;                       // PT_THETA_TAB 2: waves with at most this many sampling lanes use it
     int dark;                              // every DIFFUSE / SPECULAR material is dark (finish_path's skip)
+    // Last-ray rule (dark scenes): emit_on != 0 and a path's last ray rejected by
+    // emit_reject against [emit_lo, emit_hi] (the union of the leaf boxes that hold an EMIT
+    // triangle) ends the path at +0 without tracing that ray. Read from the kernarg segment at
+    // the use (KernargEmitReject); the hipRTC scene kernel holds the box as literals instead.
+    int emit_on;
+    float emit_lo_x, emit_lo_y, emit_lo_z, emit_hi_x, emit_hi_y, emit_hi_z;
     // Flagged slab (dark scenes, round 5): only a path that does not end dark stores its record,
     // and sets its bit in `flags`; the accumulation adds only flagged records. An unflagged
     // record would be +0, and adding +0 changes no running sum (a sum that starts at +0 is never
@@ -282,6 +289,35 @@ __device__ __forceinline__ int part_row(const TraceArgs& A, int r) {
     const int k = (int)fdiv((uint32_t)r, A.div_band), i = r - k * A.band_rows;
     return (k * A.part_count + A.part_index) * A.band_rows + i;
 }
+
+// The kernel arguments re-read from the kernarg segment (one TraceArgs at offset 0): the
+// fused accumulation's fields are loaded where they are used instead of being held in
+// SGPRs for the whole megakernel (they would push other arguments into VGPR spill lanes).
+__device__ __forceinline__ const __attribute__((address_space(4))) TraceArgs* kernarg_args() {
+    const __attribute__((address_space(4))) TraceArgs* K =
+        (const __attribute__((address_space(4))) TraceArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(K));
+    return K;
+}
+
+// The last-ray rule of shade, by where the emitter box E comes from.
+// NoEmitReject: not compiled in (caller-supplied rays and gradients, pt_paths.hip, pt_grad.hip).
+struct NoEmitReject {
+    static constexpr bool kCompiled = false;
+    __device__ __forceinline__ static bool on() { return false; }
+    __device__ __forceinline__ static bool rejected(v3, v3) { return false; }
+};
+// The render kernels that do not know the scene: flag and box from the kernarg segment
+// (scalar loads at the use, as the camera fields).
+struct KernargEmitReject {
+    static constexpr bool kCompiled = true;
+    __device__ __forceinline__ static bool on() { return kernarg_args()->emit_on != 0; }
+    __device__ __forceinline__ static bool rejected(v3 o, v3 d) {
+        const auto* K = kernarg_args();
+        return emit_reject(v3{K->emit_lo_x, K->emit_lo_y, K->emit_lo_z}, v3{K->emit_hi_x, K->emit_hi_y, K->emit_hi_z}, o,
+                           d);
+    }
+};
 
 struct NodeBox {
     v3 lb, rt;
@@ -367,6 +403,7 @@ struct TableBoxMask {
     static constexpr int kBoxes = 0;
     static constexpr uint16_t kBoxTab[1] = {0};
     static constexpr bool kDark = false;
+    using EmitRej = KernargEmitReject;  // the last-ray rule: flag and box from the kernel arguments
     __device__ __forceinline__ static unsigned long long mask(const TraceArgs& A, v3 o, v3 inv) {
         const float(*box)[6] = A.flat.box;
         unsigned long long m = 0;
@@ -1382,16 +1419,6 @@ __device__ __forceinline__ Pool pool_start(const TraceArgs& A) {
     return p;
 }
 
-// The kernel arguments re-read from the kernarg segment (one TraceArgs at offset 0): the
-// fused accumulation's fields are loaded where they are used instead of being held in
-// SGPRs for the whole megakernel (they would push other arguments into VGPR spill lanes).
-__device__ __forceinline__ const __attribute__((address_space(4))) TraceArgs* kernarg_args() {
-    const __attribute__((address_space(4))) TraceArgs* K =
-        (const __attribute__((address_space(4))) TraceArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(K));
-    return K;
-}
-
 // Radiance slab layout: [sample][pixel][rgb], one 12-B record per sample (a finished path
 // stores it with one instruction; the [rgb][sample][pixel] planes of rounds 1-3 took three:
 // +0.1-0.5 %, profiles/r04_slab_rgb). Sample s of pixel q:
@@ -1674,21 +1701,31 @@ __device__ __forceinline__ void camera_ray(const TraceArgs& A, int q, int s, Lcg
     o = v3{C.pos_x, C.pos_y, C.pos_z};
 }
 
+// What shade returns: the path goes on, ends with this segment's radiance, or ends early
+// at +0 with its last ray not traced (the caller credits that ray).
+constexpr int kShadeGo = 0, kShadeEnd = 1, kShadeEndEarly = 2;
+
 // trace() after BVH::intersect (render.h:41-57) for segment k of the path. Returns
-// true when the path ends here (L = this segment's radiance); otherwise records
+// non-zero when the path ends here (L = this segment's radiance); otherwise records
 // (tri, cos) for the fold and moves (o, d) to the next segment.
+// Rej (the last-ray rule): when the next segment is the path's last (trace(depth 1): its
+// only possible contribution is an emitter's emit_color, render.h:44-46), the rule is on
+// (a dark scene) and emit_reject proves the new ray tests no emitter triangle, that
+// segment returns +0 whatever it hits (a miss, or emission +0 + 0 * finite albedo), and the
+// levels above unwind +0 to +0 (finish_path's dark skip): the path ends here with L = +0,
+// kShadeEndEarly, with k as it was (the skipped level's record is written but never read).
 // kSpecular = false: the scene has no SPECULAR material (hipRTC kernels know the scene),
 // so the specular sampler is not compiled in.
 // kIds: `tris` is the wide path's nrm array ({n.xyz, material id} per triangle) and `mats`
 // the distinct-material table; the path record then holds the material row, not the
 // triangle (finish_path reads the same table). Otherwise mats/tris are per triangle.
-template <bool kSpecular = true, typename RecT = int, bool kIds = false>
-__device__ __forceinline__ bool shade(const TraceArgs& A, const float4* __restrict__ mats,
+template <bool kSpecular = true, typename RecT = int, bool kIds = false, typename Rej = NoEmitReject>
+__device__ __forceinline__ int shade(const TraceArgs& A, const float4* __restrict__ mats,
                                       const float4* __restrict__ tris, RecT* __restrict__ rec_tri,
                                       float* __restrict__ rec_cos, int tid, int hit, float t, Lcg& g, v3& o, v3& d,
                                       int& k, v3& L) {
     L = v3{0.0f, 0.0f, 0.0f};
-    if (hit < 0) return true;  // miss -> 0 (also depth <= 0)
+    if (hit < 0) return kShadeEnd;  // miss -> 0 (also depth <= 0)
 #ifdef PT_EXP_DUP_SHADE  // measurement only: the hit record and material reads, face-forward and hit point once more
     {
         int h2 = hit;
@@ -1712,14 +1749,15 @@ __device__ __forceinline__ bool shade(const TraceArgs& A, const float4* __restri
     const int type = __float_as_int(m0.x);
     if (type == PT_MAT_EMIT) {
         L = v3{m1.x, m1.y, m1.z};
-        return true;
+        return kShadeEnd;
     }
-    if (k + 1 >= A.depth) {
+    const int depth = A.depth;
+    if (k + 1 >= depth) {
         // Last segment: trace(depth-1 == 0) returns 0, so the result is
         // emission + ((2*0)*albedo)*cos; the BRDF draw only advanced the
         // per-sample stream, which ends here.
         L = v3{m1.x + 0.0f * m0.y, m1.y + 0.0f * m0.z, m1.z + 0.0f * m0.w};
-        return true;
+        return kShadeEnd;
     }
     v3 n;
     if constexpr (kIds) {
@@ -1791,8 +1829,18 @@ __device__ __forceinline__ bool shade(const TraceArgs& A, const float4* __restri
     rec_cos[k * kBlock + tid] = dot(n, nd);
     o = add(hp, scale(n, 1e-4f));  // SHIFT_BIAS, render.h:16, 52
     d = nd;
+    if constexpr (Rej::kCompiled) {
+        // the next segment (k + 1) is the last and cannot reach an emitter: L stays +0, and k
+        // stays too (the record just written is not read: the other lanes' writes issue anyway).
+        // No branch per lane: the test is a few compares, the outcome two selects.
+        if (Rej::on()) {  // wave-uniform
+            const bool early = ((int)(k + 2 >= depth) & (int)Rej::rejected(o, d)) != 0;
+            k += early ? 0 : 1;
+            return early ? kShadeEndEarly : kShadeGo;
+        }
+    }
     k++;
-    return false;
+    return kShadeGo;
 }
 
 // Slab record of sample s of pixel q (the radiance slab is [sample][pixel][rgb]).
@@ -1917,6 +1965,16 @@ __device__ __forceinline__ void count_rays_wave(const TraceArgs& A, int lane, un
     if (lane == 0) atomicAdd(A.ctr + 1, n_rays);
 }
 
+// Paths the last-ray rule ended early (shade: kShadeEndEarly), counted only in builds with
+// PT_COUNT_EARLY (test hook: the offline render kernels are built with it, the hipRTC scene
+// kernel takes it through PT_RTC_DEFINES); ctr[4], read by pt_debug_ctx_emit_reject.
+#ifndef PT_COUNT_EARLY
+#define PT_COUNT_EARLY 0
+#endif
+__device__ __forceinline__ void count_early_wave(const TraceArgs& A, int lane, unsigned long long n_early) {
+    if (PT_COUNT_EARLY && lane == 0 && n_early) atomicAdd(A.ctr + 4, n_early);
+}
+
 // The megakernel body of the flat path (scenes with <= 64 leaves).
 // BoxMask: the leaf-box test (the kernel-argument table, or the hipRTC-generated one with
 // the scene's planes as constants). One loop iteration = one path segment of every lane.
@@ -1987,6 +2045,7 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
     v3 o{0, 0, 0}, d{0, 0, 0};
     int k = 0;
     unsigned long long n_rays = 0;  // this wave's segments (wave-uniform)
+    unsigned long long n_early = 0;  // PT_COUNT_EARLY: paths the last-ray rule ended
     Pool pool = pool_start(A);
 #ifdef PT_STAMPS
     uint64_t stamp_acc[kStampSections] = {};
@@ -2096,14 +2155,22 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
         }
         PT_STAMP(st_c)
 
-        bool end = false;
+        int sh = kShadeGo;
         v3 L{0.0f, 0.0f, 0.0f};
         if (PT_PRIO_SHADE) __builtin_amdgcn_s_setprio(PT_PRIO_SHADE);
         if (active) {
             const FlatRecs R = flat_records(lds4);
-            end = shade<BoxMask::kSpecular>(A, mats, tris, R.tri, R.cos, fresh_tid(), hit, t, g, o, d, k, L);
+            sh = shade<BoxMask::kSpecular, uint16_t, false, typename BoxMask::EmitRej>(A, mats, tris, R.tri, R.cos,
+                                                                                       fresh_tid(), hit, t, g, o, d, k, L);
         }
         if (PT_PRIO_SHADE) __builtin_amdgcn_s_setprio(0);
+        const bool end = sh != kShadeGo;
+        if constexpr (BoxMask::EmitRej::kCompiled) {
+            // a path ended early still counts its last ray (the reference's BVH::intersect calls)
+            const unsigned long long ne = (unsigned long long)__popcll(__ballot(sh == kShadeEndEarly));
+            n_rays += ne;
+            if (PT_COUNT_EARLY) n_early += ne;
+        }
         PT_STAMP(st_d)
         if (end) {
             if (PT_PRIO_FOLD) __builtin_amdgcn_s_setprio(PT_PRIO_FOLD);
@@ -2128,6 +2195,7 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
 #endif
     drain_accumulate(A, lane);
     count_rays_wave(A, lane, n_rays);
+    count_early_wave(A, lane, n_early);
 }
 
 #ifndef PT_FLAT_ONLY
@@ -2168,6 +2236,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
     v3 o{0, 0, 0}, d{0, 0, 0};
     int k = 0;
     unsigned long long n_rays = 0;  // this wave's segments (wave-uniform)
+    unsigned long long n_early = 0;  // PT_COUNT_EARLY: paths the last-ray rule ended
     Pool pool = pool_start(A);
 
     while (true) {
@@ -2213,16 +2282,24 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
                 hit = kLdsScene ? intersect_tree<false>(s_nodes, s_tris, stk, tid, o, d, inv, t)
                                 : intersect_tree<false>(A.nodes, A.tris, stk, tid, o, d, inv, t);
         }
-        bool end = false;
+        int sh = kShadeGo;
         v3 L{0.0f, 0.0f, 0.0f};
-        if (active) end = shade(A, mats, tris, rec_tri, rec_cos, tid, hit, t, g, o, d, k, L);
-        if (end) {
+        if (active)
+            sh = shade<true, int, false, KernargEmitReject>(A, mats, tris, rec_tri, rec_cos, tid, hit, t, g, o, d, k, L);
+        {
+            // a path ended early still counts its last ray (the reference's BVH::intersect calls)
+            const unsigned long long ne = (unsigned long long)__popcll(__ballot(sh == kShadeEndEarly));
+            n_rays += ne;
+            if (PT_COUNT_EARLY) n_early += ne;
+        }
+        if (sh != kShadeGo) {
             finish_path(A, mats, rec_tri, rec_cos, tid, k, L, slab_index(A, s, q));
             active = false;
         }
     }
     drain_accumulate(A, lane);
     count_rays_wave(A, lane, n_rays);
+    count_early_wave(A, lane, n_early);
 }
 
 // The megakernel body for big scenes (wide tree read through L1/L2/MALL, its top levels
@@ -2286,6 +2363,7 @@ __device__ __forceinline__ void trace_body_wide(const TraceArgs& A) {
     int cur = 0, sp = 0;
     int qn = 0;  // wave-uniform queue length
     unsigned long long n_rays = 0;  // this wave's segments (wave-uniform)
+    unsigned long long n_early = 0;  // PT_COUNT_EARLY: paths the last-ray rule ended
     Pool pool = pool_start(A);
     const int thresh = A.wide_thresh;
     unsigned long long d_rounds = 0, d_ents = 0, f_rounds = 0, f_ents = 0;  // drain counts (PT_STAMPS)
@@ -2437,13 +2515,16 @@ __device__ __forceinline__ void trace_body_wide(const TraceArgs& A) {
 #ifdef PT_STAMPS
         stamp_acc[11] += (uint64_t)__popcll(__ballot(done));
 #endif
+        int sh = kShadeGo;
         if (done) {
             done = false;
             const unsigned long long kb = best[fresh_tid()];
             const int hit = (uint32_t)kb == 0xffffffffu ? -1 : (int)(uint32_t)kb;
             const float t = hit < 0 ? 1e30f : __uint_as_float((uint32_t)(kb >> 32));
             v3 L;
-            const bool end = shade<true, RecW, true>(A, mats, nrm, rec_tri, rec_cos, fresh_tid(), hit, t, g, o, d, k, L);
+            sh = shade<true, RecW, true, KernargEmitReject>(A, mats, nrm, rec_tri, rec_cos, fresh_tid(), hit, t, g, o, d,
+                                                            k, L);
+            const bool end = sh != kShadeGo;  // early or not: the same end of the path below
             PT_STAMP(st_e)
             PT_STAMP_ADD(3, st_d, st_e)
 #ifdef PT_STAMPS
@@ -2456,6 +2537,12 @@ __device__ __forceinline__ void trace_body_wide(const TraceArgs& A) {
             }
             PT_STAMP(st_f)
             PT_STAMP_ADD(4, st_e, st_f)
+        }
+        {
+            // a path ended early still counts its last ray (the reference's BVH::intersect calls)
+            const unsigned long long ne = (unsigned long long)__popcll(__ballot(sh == kShadeEndEarly));
+            n_rays += ne;
+            if (PT_COUNT_EARLY) n_early += ne;
         }
     }
 #ifdef PT_STAMPS
@@ -2484,6 +2571,7 @@ __device__ __forceinline__ void trace_body_wide(const TraceArgs& A) {
 #endif
     drain_accumulate(A, lane);
     count_rays_wave(A, lane, n_rays);
+    count_early_wave(A, lane, n_early);
 }
 #endif  // PT_FLAT_ONLY
 

@@ -392,8 +392,21 @@ class Renderer:
         """How this context renders its scene (test hook pt_debug_ctx_flags)."""
         out = (C.c_int32 * 5)()
         check(lib().pt_debug_ctx_flags(self.h, out))
-        return {"albedo_x2": bool(out[0]), "specular": bool(out[1]), "rtc": bool(out[2]), "wide_nodes": out[3],
-                "dark": bool(out[4])}
+        d = {"albedo_x2": bool(out[0]), "specular": bool(out[1]), "rtc": bool(out[2]), "wide_nodes": out[3],
+             "dark": bool(out[4])}
+        if hasattr(lib(), "pt_debug_ctx_emit_reject"):  # absent from older builds used in A/B runs
+            on, box = C.c_int32(0), (C.c_float * 6)()
+            check(lib().pt_debug_ctx_emit_reject(self.h, C.byref(on), box, None))
+            d["emit_reject"] = bool(on.value)
+            d["emit_box"] = list(box)
+        return d
+
+    def early_ends(self) -> int:
+        """Paths the last-ray rule ended in this context's last render (test hook; counted by the
+        offline kernels, and by the hipRTC scene kernel under PT_RTC_DEFINES=PT_COUNT_EARLY=1)."""
+        n = C.c_uint64(0)
+        check(lib().pt_debug_ctx_emit_reject(self.h, None, None, C.byref(n)))
+        return n.value
 
     PLAN_KEYS = ("kernel_path", "flat", "wide", "pairs", "pair_queue", "lds_bytes", "lds_scene", "wide_rows",
                  "wide_queue", "wide_top", "blocks_per_cu", "batch", "per_item", "fused", "tail", "flags_pm",

@@ -13,8 +13,13 @@ wave-iteration the lanes trace one segment each of paths at mixed depths. Two qu
 2. Specular rejection loop (`material.h:20-23`): lanes shading a SPECULAR hit loop until a
    jittered reflection leaves the surface; a wave pays max-over-lanes trips. Mean trips per
    specular lane against the wave's max.
+3. Last-ray rule: a path's last ray (segment depth - 1) that provably fails
+   every emitter leaf box (emit_reject, pt_math.h) is not traced; the bounce that made it
+   credits it and the lane takes the next path. Share of last rays and of rejected ones among
+   all rays, rays credited per wave-iteration, (lane, leaf) pairs and pair rounds per
+   iteration, each with and without the rule.
 
-usage: python scripts/wave_sim.py [--scene cornell|mcornell] [--rough R] [--paths N]
+usage: python scripts/wave_sim.py [--scene cornell|mcornell] [--rough R] [--paths N] [--depth D]
 """
 import argparse
 import json
@@ -156,6 +161,50 @@ def passes(lb, rt, o, d):
     return tmin <= tmax
 
 
+def leaf_boxes(nodes):
+    """(lb, rt, first, last) of every leaf of the tree."""
+    out, st = [], [0]
+    while st:
+        i = st.pop()
+        if nodes[i]["left"] < 0 and nodes[i]["right"] < 0:
+            out.append((np.array(nodes[i]["lb"], dtype=np.float64), np.array(nodes[i]["rt"], dtype=np.float64),
+                        int(nodes[i]["tri_start"]), int(nodes[i]["tri_end"])))
+        else:
+            st += [int(nodes[i]["left"]), int(nodes[i]["right"])]
+    return out
+
+
+def emit_reject(lo, hi, o, d):
+    """pt_math.h's predicate: on some axis the origin is outside [lo, hi] and d points away."""
+    return (((o < lo[None]) & (d < 0) | (o > hi[None]) & (d > 0)) & (np.abs(d) < 2)).any(axis=1)
+
+
+def last_ray_rule(segs, nodes, tri_idx, mtype, depth):
+    """Per path: True when its last ray exists and the rule rejects it."""
+    lo, hi = np.full(3, np.inf), np.full(3, -np.inf)
+    for lb, rt, first, last in leaf_boxes(nodes):
+        if any(mtype[int(tri_idx[i])] == EMIT for i in range(first, last + 1)):
+            lo, hi = np.minimum(lo, lb), np.maximum(hi, rt)
+    has = np.array([len(s) == depth and depth >= 2 for s in segs])
+    rej = np.zeros(len(segs), dtype=bool)
+    if has.any():
+        idx = np.nonzero(has)[0]
+        o = np.array([segs[i][-1][0] for i in idx])
+        d = np.array([segs[i][-1][1] for i in idx])
+        rej[idx] = emit_reject(lo, hi, o, d)
+    return has, rej
+
+
+def pair_stats(its, leaves, credited):
+    """Means per wave-iteration: rays credited, (lane, leaf) pairs, rounds of 64 pairs."""
+    pairs = []
+    for o, d, _ in its:
+        pairs.append(sum(int(passes(lb, rt, o, d).sum()) for lb, rt, _, _ in leaves))
+    pairs = np.array(pairs)
+    return {"wave_iterations": len(its), "rays_credited_per_iteration": credited / len(its),
+            "pairs_per_iteration": float(pairs.mean()), "pair_rounds_per_iteration": float(np.ceil(pairs / 64).mean())}
+
+
 def simulate(segs, trips, lanes=64):
     """wave-iterations: each lane traces its path's next segment; an ended path's lane takes
     the next path (work item). Returns per iteration the (o, d) of the active lanes and the
@@ -193,7 +242,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     a = ap.parse_args()
     rng = np.random.default_rng(a.seed)
-    sc, tris, mtype, rgh, nodes, _ = load(a.scene, a.rough)
+    sc, tris, mtype, rgh, nodes, tri_idx = load(a.scene, a.rough)
     segs, trips = trace_paths(sc, tris, mtype, rgh, a.paths, a.depth, rng)
     its = simulate(segs, trips)
     nseg = sum(len(s) for s in segs)
@@ -219,6 +268,21 @@ def main():
             "mean_max_trips_per_wave": float(np.mean([max(t) for t in waves])),
             "trip_histogram": np.bincount(np.array(spec_lanes), minlength=8)[:12].tolist(),
         }
+    # 3. the last-ray rule: the rejected last segments leave the paths, their rays stay credited
+    has, rej = last_ray_rule(segs, nodes, tri_idx, mtype, a.depth)
+    leaves = leaf_boxes(nodes)
+    full = sum(len(o) for o, _, _ in its)
+    cut = [s[:-1] if r else s for s, r in zip(segs, rej)]
+    its_rule = simulate(cut, trips)
+    traced = sum(len(o) for o, _, _ in its_rule)
+    # rays credited in the simulated (steady-state) iterations: the traced ones and the early
+    # ends' share of them (the drain tail is cut from both runs)
+    out["last_ray_rule"] = {
+        "last_rays_over_all_rays": float(has.sum()) / nseg, "rejected_over_all_rays": float(rej.sum()) / nseg,
+        "rejected_over_last_rays": float(rej.sum()) / max(1, int(has.sum())),
+        "without": pair_stats(its, leaves, full),
+        "with": pair_stats(its_rule, leaves, traced * nseg / (nseg - float(rej.sum()))),
+    }
     print(json.dumps(out, indent=1))
 
 
