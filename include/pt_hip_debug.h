@@ -92,6 +92,10 @@ int pt_debug_scene_dark(const pt_scene* scene);
  * rays: box6[6i..] = {E lb.xyz, E rt.xyz}, org / dir 3 floats each -> out[i] = 1 if ray i provably
  * fails the reference's slab test for every box inside E. */
 int pt_debug_emit_reject(const float* box6, const float* org, const float* dir, int64_t n, uint8_t* out);
+/* Test hook, no device needed: the flat kernels' form of the rule (emit_slab_reject, pt_math.h) on
+ * n rays: box6 and org as above, inv 3 floats each (the kernels pass 1 / dir) -> out[i] = 1 if E
+ * itself fails the slab test, under the predicate's guard, or E is empty (lb > rt on an axis). */
+int pt_debug_emit_slab_reject(const float* box6, const float* org, const float* inv, int64_t n, uint8_t* out);
 /* Test hook, no device needed: the emitter box the host computes for `scene` (the union of the
  * tree's leaf boxes that hold an EMIT triangle; lb = +inf, rt = -inf when there is none, which
  * rejects every last ray). Returns 1 if the rule is on (a dark scene, PT_EMIT_REJECT not 0), 0 if

@@ -128,6 +128,7 @@ struct PackedScene {
 // of the tree's leaf boxes that hold an EMIT triangle; lo = +inf, hi = -inf when there is none.
 struct EmitBox {
     bool on = false;  // the rule applies (a dark scene; PT_EMIT_REJECT=0 turns it off)
+    bool sign_only = false;  // test hook PT_EMIT_REJECT=sign: the flat kernels keep the sign rule alone
     float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
 };
 

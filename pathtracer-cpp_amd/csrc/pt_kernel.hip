@@ -784,7 +784,7 @@ int fill_trace_args(pt_ctx* c, const RenderPlan& P, const pt_camera* cam, const 
     A.work = c->d_ctr;
     A.ctr = c->d_ctr;
     A.dark = c->dark ? 1 : 0;
-    A.emit_on = c->emit.on ? 1 : 0;
+    A.emit_on = emit_mode(c->emit);
     A.emit_lo_x = c->emit.lo[0], A.emit_lo_y = c->emit.lo[1], A.emit_lo_z = c->emit.lo[2];
     A.emit_hi_x = c->emit.hi[0], A.emit_hi_y = c->emit.hi[1], A.emit_hi_z = c->emit.hi[2];
     fill_camera(A, cam, P.shape, prm);
@@ -2004,6 +2004,16 @@ int pt_debug_emit_reject(const float* box6, const float* org, const float* dir, 
     for (int64_t i = 0; i < n; i++) {
         const float *b = box6 + 6 * i, *o = org + 3 * i, *d = dir + 3 * i;
         out[i] = emit_reject(v3{b[0], b[1], b[2]}, v3{b[3], b[4], b[5]}, v3{o[0], o[1], o[2]}, v3{d[0], d[1], d[2]}) ? 1 : 0;
+    }
+    return PT_OK;
+}
+
+// Test hook (no device needed): emit_slab_reject (pt_math.h) on n rays against n boxes.
+int pt_debug_emit_slab_reject(const float* box6, const float* org, const float* inv, int64_t n, uint8_t* out) {
+    if (!box6 || !org || !inv || !out || n < 0) return set_error(PT_E_ARG, "pt_debug_emit_slab_reject: bad argument");
+    for (int64_t i = 0; i < n; i++) {
+        const float *b = box6 + 6 * i, *o = org + 3 * i, *v = inv + 3 * i;
+        out[i] = emit_slab_reject(v3{b[0], b[1], b[2]}, v3{b[3], b[4], b[5]}, v3{o[0], o[1], o[2]}, v3{v[0], v[1], v[2]}) ? 1 : 0;
     }
     return PT_OK;
 }

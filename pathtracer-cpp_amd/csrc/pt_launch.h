@@ -97,6 +97,9 @@ bool albedo_x2_ok(const PackedScene& ps);        // the flat kernel may unwind w
 // The last-ray rule (§3.15): on in a dark scene (`dark`: scene_dark), with the union of the leaf
 // boxes that hold an EMIT triangle. Test hook PT_EMIT_REJECT=0 turns it off.
 EmitBox scene_emit_box(const PackedScene& ps, bool dark);
+// TraceArgs::emit_on for a box: 0 off, else which form the flat kernels run (kEmitSlab,
+// kEmitSignOnly, kEmitSlabEmpty in pt_trace.h); the tree and wide kernels read it as on / off.
+int emit_mode(const EmitBox& e);
 
 // ---- the binary walk of pt_query.hip and pt_paths.hip.
 // Where a launch keeps the scene, the walk's stack and the path records, and its grid.

@@ -281,7 +281,18 @@ EmitBox scene_emit_box(const PackedScene& ps, bool dark) {
         }
     }
     e.on = true;
+    // the flat kernels use the slab test of E (emit_slab_reject); PT_EMIT_REJECT=sign keeps them
+    // on the sign rule alone (the scene kernel through PT_EMIT_SIGN_ONLY in its source, the table
+    // kernels through TraceArgs::emit_on): the A/B of the two rules
+    const char* h = hook_env("PT_EMIT_REJECT");
+    e.sign_only = h && strcmp(h, "sign") == 0;
     return e;
+}
+
+int emit_mode(const EmitBox& e) {
+    if (!e.on) return 0;
+    if (e.sign_only) return kEmitSignOnly;
+    return emit_box_empty(v3{e.lo[0], e.lo[1], e.lo[2]}, v3{e.hi[0], e.hi[1], e.hi[2]}) ? kEmitSlabEmpty : kEmitSlab;
 }
 
 // Whether the flat kernel may unwind with pre-doubled albedo (finish_path<., true>: L * 2a

@@ -212,6 +212,69 @@ PT_HD bool emit_reject(v3 elb, v3 ert, v3 o, v3 d) {
             emit_reject_axis(elb.z, ert.z, o.z, d.z)) != 0;
 }
 
+// Whether ray (o, inv = 1 / d) provably fails slab_hit (aabb.h:20-29) for EVERY box [lb, rt]
+// inside E = [elb, ert] (elb <= lb <= rt <= ert per axis, no NaN in the boxes; scene_emit_box
+// turns the rule off otherwise): E itself fails the reference's slab test. The flat kernels
+// use it in place of emit_reject: it rejects every ray emit_reject rejects
+// whenever the guard below holds (tests/test_last_ray_slab.py), and the rays that miss E
+// while facing it.
+// Guard: every component of inv is finite and non-zero and o is finite. Otherwise the answer
+// is "not rejected" and the ray is traced as before (no fallback to the sign rule).
+// Proof, for one box B = [lb, rt] inside a non-empty E, under the guard.
+//   * No NaN: x - o.a for a plane x is a number (finite, or +-inf when x is infinite or the
+//     difference overflows; never inf - inf, o.a is finite), and a number times a finite
+//     non-zero inv.a is a number (0 * inf needs a zero or an infinite factor: the only zero
+//     is x - o.a = 0, whose other factor is finite).
+//   * Monotone: float subtraction and multiplication round monotonically, so f(x) =
+//     (x - o.a) * inv.a is non-decreasing in x for inv.a > 0 and non-increasing for inv.a < 0
+//     (overflow to +-inf and underflow to +-0 keep the order; -0 and +0 compare equal). With
+//     elb.a <= lb.a <= rt.a <= ert.a that gives, for either sign of inv.a,
+//         min(t1, t2)_B >= min(t1, t2)_E   and   max(t1, t2)_B <= max(t1, t2)_E.
+//   * The folds: without NaN the reference's std::max(a, b) = (a < b) ? b : a, std::min and
+//     the left folds of std::min({..}) / std::max({..}) return a value equal (==) to the
+//     IEEE maximum / minimum of their operands; they can differ only in the sign of a zero.
+//     Minimum and maximum are monotone in every operand, so tmin_B >= tmin_E and
+//     tmax_B <= tmax_E as numbers, where the E values are the IEEE ones computed here.
+//   * E fails: tmax_E < 0 gives tmax_B <= tmax_E < 0, so B fails `!(tmax < 0)`; tmin_E > tmax_E
+//     gives tmin_B >= tmin_E > tmax_E >= tmax_B, so B fails `tmin <= tmax`. Both comparisons are
+//     strict and between numbers, so the sign of a zero cannot change either.
+//   * A failed box is not entered: BVH::intersect tests none of B's triangles, and an
+//     ancestor's box failing only removes more tests.
+// NaN in o or inv fails the guard; the claim is a conjunction of comparisons that are false
+// for NaN, never the negation of a hit test.
+// A flat axis of E (elb.a == ert.a, the Cornell light in y) has t1 == t2: with the box as
+// literals the compiler folds that axis' min and max away.
+// Bitwise & and | as in emit_reject: straight-line compares, no branches per lane.
+PT_HD bool finite_nonzero(float x) { return ((int)(__builtin_fabsf(x) < __builtin_inff()) & (int)(x != 0.0f)) != 0; }
+// behind_only: the `tmax < 0` term alone, E lies behind the ray on some axis. Under the guard
+// that is emit_reject's condition without its bound on |d|: max(t1, t2) < 0 on axis a means
+// both differences are non-zero with the sign opposite to inv.a's, i.e. o.a < elb.a with
+// d.a < 0 or o.a > ert.a with d.a > 0, and emit_reject's proof gives the converse for |d.a| < 2.
+// The table kernels' sign-only hook runs this (a select on a flag, no second predicate in the
+// kernel); the hipRTC scene kernel's runs emit_reject itself.
+PT_HD bool emit_slab_reject_nonempty(v3 elb, v3 ert, v3 o, v3 inv, bool behind_only = false) {
+    const int guard = (int)finite_nonzero(inv.x) & (int)finite_nonzero(inv.y) & (int)finite_nonzero(inv.z) &
+                      (int)(__builtin_fabsf(o.x) < __builtin_inff()) & (int)(__builtin_fabsf(o.y) < __builtin_inff()) &
+                      (int)(__builtin_fabsf(o.z) < __builtin_inff());
+    const float t1x = (elb.x - o.x) * inv.x, t1y = (elb.y - o.y) * inv.y, t1z = (elb.z - o.z) * inv.z;
+    const float t2x = (ert.x - o.x) * inv.x, t2y = (ert.y - o.y) * inv.y, t2z = (ert.z - o.z) * inv.z;
+    const float tmax = __builtin_fminf(__builtin_fminf(__builtin_fmaxf(t1x, t2x), __builtin_fmaxf(t1y, t2y)),
+                                       __builtin_fmaxf(t1z, t2z));
+    const float tmin = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(t1x, t2x), __builtin_fminf(t1y, t2y)),
+                                       __builtin_fminf(t1z, t2z));
+    return (guard & ((int)(tmax < 0.0f) | ((int)!behind_only & (int)(tmin > tmax)))) != 0;
+}
+// E empty (scene_emit_box's encoding of "no emitter leaf": elb = +inf, ert = -inf): there is no
+// box to hit, every last ray is rejected, whatever o and inv hold (the slab arithmetic on the
+// inverted infinite box would pass it). With the box as literals the test folds at compile
+// time; the kernels that take the box as an argument decide it from a flag, wave-uniformly.
+PT_HD bool emit_box_empty(v3 elb, v3 ert) {
+    return ((int)(elb.x > ert.x) | (int)(elb.y > ert.y) | (int)(elb.z > ert.z)) != 0;
+}
+PT_HD bool emit_slab_reject(v3 elb, v3 ert, v3 o, v3 inv) {
+    return emit_box_empty(elb, ert) ? true : emit_slab_reject_nonempty(elb, ert, o, inv);
+}
+
 // ------------------------------------------------------------------ Möller–Trumbore (triangle.h:25-44)
 // e1 = v2 - v1 and e2 = v3 - v1 are precomputed on the host with the same float ops.
 PT_HD bool tri_hit(v3 v1, v3 e1, v3 e2, v3 o, v3 d, float& t) {

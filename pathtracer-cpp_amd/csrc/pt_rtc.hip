@@ -286,11 +286,19 @@ std::string flat_mask_source(const std::vector<f4>& leaves, int n, bool specular
               "        __device__ __forceinline__ static bool rejected(v3 o, v3 d) {\n"
               "            return emit_reject(v3{" + litf(emit.lo[0]) + ", " + litf(emit.lo[1]) + ", " + litf(emit.lo[2]) +
               "}, v3{" + litf(emit.hi[0]) + ", " + litf(emit.hi[1]) + ", " + litf(emit.hi[2]) + "}, o, d);\n"
+              "        }\n"
+              // the slab rule, which the flat body runs with the inv it carries (shade_inv); under
+              // PT_EMIT_SIGN_ONLY (test hook) the member above alone, and no carried inv
+              "        static constexpr bool kSlab = !PT_EMIT_SIGN_ONLY;\n"
+              "        __device__ __forceinline__ static bool rejected_slab(v3 o, v3, v3 inv) {\n"
+              "            return emit_slab_reject(v3{" + litf(emit.lo[0]) + ", " + litf(emit.lo[1]) + ", " + litf(emit.lo[2]) +
+              "}, v3{" + litf(emit.hi[0]) + ", " + litf(emit.hi[1]) + ", " + litf(emit.hi[2]) + "}, o, inv);\n"
               "        }\n    };\n";
     return std::string("#ifndef PT_FLAT_SIGN_MASK\n#define PT_FLAT_SIGN_MASK 0\n#endif\n#define KSIGN (PT_FLAT_SIGN_MASK && ") +
            (sign ? "1" : "0") + ")\n" + "#define KBOX " + (nbox > 0 ? "(!KSIGN)" : "0") + "\n" +
            "namespace pt {\nstruct SceneBoxMask {\n    static constexpr bool kSignMask = KSIGN;\n"
-           "    static constexpr bool kBoxPairs = KBOX;\n    static constexpr int kBoxes = " + std::to_string(nbox) +
+           "    static constexpr bool kBoxPairs = KBOX;\n    static constexpr bool kCamInvGen = PT_CAM_INV == 2;\n"
+           "    static constexpr int kBoxes = " + std::to_string(nbox) +
            ";\n    static constexpr uint16_t kBoxTab[" + std::to_string(std::max<size_t>(1, box_tab.size())) + "] = " + tabs +
            ";\n    static constexpr bool kMask32 = " +
            (n <= 32 ? "true" : "false") + ";\n    static constexpr bool kSingleTri = " + (single ? "true" : "false") +
@@ -362,7 +370,8 @@ std::string rtc_flat_source(const std::vector<f4>& leaves, int n, bool specular,
     // threadIdx.x re-read at each use (fresh_tid) only in scenes with the specular sampler:
     // without it the kernel has VGPRs to spare at 8 waves and plain threadIdx.x is +0.5-1.2 %
     // (configs 2, 5); with it plain threadIdx.x costs SGPR spill lanes, -0.3 % (config 3)
-    return fl + "\n" + rtc_defines() + "#define PT_WAVES " + std::to_string(rtc_waves()) +
+    return fl + "\n" + rtc_defines() + (emit.on && emit.sign_only ? "#define PT_EMIT_SIGN_ONLY 1\n" : "") +
+           "#define PT_WAVES " + std::to_string(rtc_waves()) +
            "\n#define PT_FLAT_ONLY 1\n#ifndef PT_CAM_KERNARG\n#define PT_CAM_KERNARG 0\n#endif\n"
            "#ifndef PT_FRESH_TID\n#define PT_FRESH_TID " + (specular ? "1" : "0") + "\n#endif\n"
            "typedef __hip_internal::int32_t int32_t; typedef __hip_internal::uint32_t uint32_t;\n"

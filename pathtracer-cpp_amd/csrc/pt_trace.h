@@ -269,6 +269,8 @@ struct TraceArgs {
     // emit_reject against [emit_lo, emit_hi] (the union of the leaf boxes that hold an EMIT
     // triangle) ends the path at +0 without tracing that ray. Read from the kernarg segment at
     // the use (KernargEmitReject); the hipRTC scene kernel holds the box as literals instead.
+    // The flat kernels test the slab of E itself (emit_slab_reject) and read emit_on as the form
+    // to run (kEmitSlab, kEmitSignOnly, kEmitSlabEmpty: KernargEmitSlabReject).
     int emit_on;
     float emit_lo_x, emit_lo_y, emit_lo_z, emit_hi_x, emit_hi_y, emit_hi_z;
     // Flagged slab (dark scenes, round 5): only a path that does not end dark stores its record,
@@ -317,6 +319,38 @@ struct KernargEmitReject {
         return emit_reject(v3{K->emit_lo_x, K->emit_lo_y, K->emit_lo_z}, v3{K->emit_hi_x, K->emit_hi_y, K->emit_hi_z}, o,
                            d);
     }
+};
+
+// The flat kernels' form (trace_body_flat carries inv = 1 / d beside d): the slab test of E,
+// emit_slab_reject. emit_on (plan_render): kEmitSlab the slab rule, kEmitSignOnly the sign rule
+// alone (test hook PT_EMIT_REJECT=sign: the A/B against the slab rule), kEmitSlabEmpty the slab
+// rule with no emitter leaf in the scene (every last ray ends early). The tree and wide
+// kernels read any non-zero value as "on" and keep the sign rule (KernargEmitReject).
+constexpr int kEmitSlab = 1, kEmitSignOnly = 2, kEmitSlabEmpty = 3;
+#ifndef PT_EMIT_SIGN_ONLY
+#define PT_EMIT_SIGN_ONLY 0  // 1: the hipRTC scene kernel keeps the sign rule alone (test hook, A/B)
+#endif
+struct KernargEmitSlabReject : KernargEmitReject {
+    static constexpr bool kSlab = true;
+    __device__ __forceinline__ static bool rejected_slab(v3 o, v3, v3 inv) {
+        const auto* K = kernarg_args();
+        const int mode = K->emit_on;  // wave-uniform
+        if (mode == kEmitSlabEmpty) return true;
+        // the sign-only hook: the slab rule's `tmax < 0` term alone, which under the guard is the
+        // sign rule (emit_slab_reject_nonempty); emit_reject's own code beside the slab test made
+        // the table kernels reserve scratch
+        return emit_slab_reject_nonempty(v3{K->emit_lo_x, K->emit_lo_y, K->emit_lo_z},
+                                         v3{K->emit_hi_x, K->emit_hi_y, K->emit_hi_z}, o, inv, mode == kEmitSignOnly);
+    }
+};
+// Whether a policy carries inv (has the slab member): the others compile shade as it was.
+template <typename Rej, typename = void>
+struct RejSlab {
+    static constexpr bool value = false;
+};
+template <typename Rej>
+struct RejSlab<Rej, decltype((void)Rej::kSlab)> {
+    static constexpr bool value = Rej::kCompiled && Rej::kSlab;
 };
 
 struct NodeBox {
@@ -400,10 +434,11 @@ struct TableBoxMask {
     static constexpr bool kAlbedoX2 = false;   // the block's material copy holds 2 * albedo (finish_path)
     static constexpr bool kDarkKnown = false;  // kDark is not known at compile time: finish_path reads A.dark
     static constexpr bool kBoxPairs = false;   // mask bits are leaves (hipRTC kernels may use box-level pairs)
+    static constexpr bool kCamInvGen = false;  // a camera ray's carried inv: start branch (60 VGPRs; generator: 64)
     static constexpr int kBoxes = 0;
     static constexpr uint16_t kBoxTab[1] = {0};
     static constexpr bool kDark = false;
-    using EmitRej = KernargEmitReject;  // the last-ray rule: flag and box from the kernel arguments
+    using EmitRej = KernargEmitSlabReject;  // the last-ray rule: flag and box from the kernel arguments
     __device__ __forceinline__ static unsigned long long mask(const TraceArgs& A, v3 o, v3 inv) {
         const float(*box)[6] = A.flat.box;
         unsigned long long m = 0;
@@ -434,6 +469,9 @@ struct FastTableMask : TableBoxMask {
     static constexpr bool kAlbedoX2 = true;
     static constexpr bool kDarkKnown = true;
     static constexpr bool kDark = true;
+    // the form that leaves each kernel without a scratch reservation at its 64 VGPRs (with the
+    // specular sampler the generator form, 61 VGPRs; without it the start branch, 60)
+    static constexpr bool kCamInvGen = kSpec;
 };
 
 // Triangle phase of the flat path for one lane: the triangles of the leaves in `mask`,
@@ -1719,11 +1757,14 @@ constexpr int kShadeGo = 0, kShadeEnd = 1, kShadeEndEarly = 2;
 // kIds: `tris` is the wide path's nrm array ({n.xyz, material id} per triangle) and `mats`
 // the distinct-material table; the path record then holds the material row, not the
 // triangle (finish_path reads the same table). Otherwise mats/tris are per triangle.
+// A policy with the slab member (RejSlab: the flat body) also gets inv = 1 / d of the new ray in
+// `inv`, computed here for the lanes whose path goes on and used by the slab test; the other
+// policies leave `inv` alone and compile what they compiled without it.
 template <bool kSpecular = true, typename RecT = int, bool kIds = false, typename Rej = NoEmitReject>
-__device__ __forceinline__ int shade(const TraceArgs& A, const float4* __restrict__ mats,
-                                      const float4* __restrict__ tris, RecT* __restrict__ rec_tri,
-                                      float* __restrict__ rec_cos, int tid, int hit, float t, Lcg& g, v3& o, v3& d,
-                                      int& k, v3& L) {
+__device__ __forceinline__ int shade_inv(const TraceArgs& A, const float4* __restrict__ mats,
+                                          const float4* __restrict__ tris, RecT* __restrict__ rec_tri,
+                                          float* __restrict__ rec_cos, int tid, int hit, float t, Lcg& g, v3& o,
+                                          v3& d, v3& inv, int& k, v3& L) {
     L = v3{0.0f, 0.0f, 0.0f};
     if (hit < 0) return kShadeEnd;  // miss -> 0 (also depth <= 0)
 #ifdef PT_EXP_DUP_SHADE  // measurement only: the hit record and material reads, face-forward and hit point once more
@@ -1829,18 +1870,32 @@ __device__ __forceinline__ int shade(const TraceArgs& A, const float4* __restric
     rec_cos[k * kBlock + tid] = dot(n, nd);
     o = add(hp, scale(n, 1e-4f));  // SHIFT_BIAS, render.h:16, 52
     d = nd;
+    if constexpr (RejSlab<Rej>::value) inv = v3{rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z)};  // bvh.h:157
     if constexpr (Rej::kCompiled) {
         // the next segment (k + 1) is the last and cannot reach an emitter: L stays +0, and k
         // stays too (the record just written is not read: the other lanes' writes issue anyway).
         // No branch per lane: the test is a few compares, the outcome two selects.
         if (Rej::on()) {  // wave-uniform
-            const bool early = ((int)(k + 2 >= depth) & (int)Rej::rejected(o, d)) != 0;
+            bool rej;
+            if constexpr (RejSlab<Rej>::value) rej = Rej::rejected_slab(o, d, inv);
+            else rej = Rej::rejected(o, d);
+            const bool early = ((int)(k + 2 >= depth) & (int)rej) != 0;
             k += early ? 0 : 1;
             return early ? kShadeEndEarly : kShadeGo;
         }
     }
     k++;
     return kShadeGo;
+}
+
+template <bool kSpecular = true, typename RecT = int, bool kIds = false, typename Rej = NoEmitReject>
+__device__ __forceinline__ int shade(const TraceArgs& A, const float4* __restrict__ mats,
+                                      const float4* __restrict__ tris, RecT* __restrict__ rec_tri,
+                                      float* __restrict__ rec_cos, int tid, int hit, float t, Lcg& g, v3& o, v3& d,
+                                      int& k, v3& L) {
+    static_assert(!RejSlab<Rej>::value, "a policy with the slab rule carries inv: shade_inv");
+    v3 unused{0.0f, 0.0f, 0.0f};
+    return shade_inv<kSpecular, RecT, kIds, Rej>(A, mats, tris, rec_tri, rec_cos, tid, hit, t, g, o, d, unused, k, L);
 }
 
 // Slab record of sample s of pixel q (the radiance slab is [sample][pixel][rgb]).
@@ -1990,6 +2045,15 @@ __device__ __forceinline__ void count_early_wave(const TraceArgs& A, int lane, u
 #ifndef PT_FRESH_TID
 #define PT_FRESH_TID 1  // 0: plain threadIdx.x (A/B hook)
 #endif
+// Where a camera ray's inv = 1 / d is computed when the body carries inv (kCarry; DESIGN.md
+// §3.15), BoxMask::kCamInvGen: in the batched generator, which runs about every second
+// iteration with many lanes, held in three VGPRs until the path starts (the headline: +1.7 %
+// against the sign rule), or in the branch that starts the path, one more reciprocal site in
+// every iteration (+0.5 %). PT_CAM_INV picks the hipRTC scene kernel's form (2 generator, 1 start
+// branch: A/B hook); the table kernels take the form under which they reserve no scratch.
+#ifndef PT_CAM_INV
+#define PT_CAM_INV 2
+#endif
 __device__ __forceinline__ int fresh_tid() {
     int t = (int)threadIdx.x;
     if (PT_FRESH_TID) asm volatile("" : "+v"(t));
@@ -2043,6 +2107,13 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
     uint32_t at = 0;
     Lcg g{0};
     v3 o{0, 0, 0}, d{0, 0, 0};
+    // kCarry (the slab form of the last-ray rule): inv = 1 / d is loop state beside d, made where
+    // the ray is made (shade_inv for a bounce, below for a camera ray), because the slab test
+    // needs it there; otherwise it is computed at the top of each iteration as before.
+    constexpr bool kCarry = RejSlab<typename BoxMask::EmitRej>::value;
+    v3 inv{0, 0, 0};
+    constexpr bool kGenInv = kCarry && BoxMask::kCamInvGen;
+    v3 next_inv{0, 0, 0};  // kGenInv: 1 / d of the prefetched camera ray (the LDS has no room for it)
     int k = 0;
     unsigned long long n_rays = 0;  // this wave's segments (wave-uniform)
     unsigned long long n_early = 0;  // PT_COUNT_EARLY: paths the last-ray rule ended
@@ -2080,6 +2151,7 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
 #endif
                 next_ray[fresh_tid()] = make_float4(nd.x, nd.y, nd.z, __uint_as_float(gn.s));
                 next_at[fresh_tid()] = item;
+                if constexpr (kGenInv) next_inv = v3{rcp_exact(nd.x), rcp_exact(nd.y), rcp_exact(nd.z)};
                 has_next = true;
             }
         }
@@ -2089,6 +2161,8 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
             at = next_at[t0];
             g.s = __float_as_uint(nr.w);
             d = v3{nr.x, nr.y, nr.z};
+            if constexpr (kGenInv) inv = next_inv;
+            else if constexpr (kCarry) inv = v3{rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z)};  // bvh.h:157
             o = v3{A.pos_x, A.pos_y, A.pos_z};
             k = 0;
             active = true;
@@ -2105,7 +2179,7 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
         if (A.depth > 0) n_rays += (unsigned long long)__popcll(__ballot(tr));
         // bvh.h:157 inv = 1 / d. Waves whose lanes all have finite inv take the IEEE
         // min/max slab test (identical result, see slab_hit_finite).
-        const v3 inv{rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z)};
+        if constexpr (!kCarry) inv = v3{rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z)};
         const bool forced = A.force_exact_slab == 1 || (A.force_exact_slab == 2 && ((tid >> 6) & 1));
         // with the sign-bit box mask (BoxMask::kSignMask) the wave's plane values must stay
         // finite: |1 / d| <= 2^60 and |o| < 2^60 (scene coordinates < 2^60: the host's
@@ -2160,8 +2234,8 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
         if (PT_PRIO_SHADE) __builtin_amdgcn_s_setprio(PT_PRIO_SHADE);
         if (active) {
             const FlatRecs R = flat_records(lds4);
-            sh = shade<BoxMask::kSpecular, uint16_t, false, typename BoxMask::EmitRej>(A, mats, tris, R.tri, R.cos,
-                                                                                       fresh_tid(), hit, t, g, o, d, k, L);
+            sh = shade_inv<BoxMask::kSpecular, uint16_t, false, typename BoxMask::EmitRej>(
+                A, mats, tris, R.tri, R.cos, fresh_tid(), hit, t, g, o, d, inv, k, L);
         }
         if (PT_PRIO_SHADE) __builtin_amdgcn_s_setprio(0);
         const bool end = sh != kShadeGo;

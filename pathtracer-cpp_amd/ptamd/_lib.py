@@ -31,7 +31,7 @@ EXPORTED = (
     "pt_bvh_intersect", "pt_ctx_intersect", "pt_ctx_render_aov",
     "pt_bvh_trace", "pt_ctx_trace", "pt_debug_ctx_plan", "pt_debug_walk_placement",
     "pt_bvh_trace_grad", "pt_ctx_trace_grad",
-    "pt_debug_emit_reject", "pt_debug_emit_box", "pt_debug_ctx_emit_reject",
+    "pt_debug_emit_reject", "pt_debug_emit_box", "pt_debug_ctx_emit_reject", "pt_debug_emit_slab_reject",
 )
 PT_MAX_DEVICES = 16
 
@@ -254,6 +254,8 @@ def lib() -> C.CDLL:
             L.pt_debug_emit_reject.argtypes = [P, P, P, C.c_int64, P]
             L.pt_debug_emit_box.argtypes = [C.POINTER(pt_scene), P]
             L.pt_debug_ctx_emit_reject.argtypes = [P, P, P, P]
+        if hasattr(L, "pt_debug_emit_slab_reject"):
+            L.pt_debug_emit_slab_reject.argtypes = [P, P, P, C.c_int64, P]
         if hasattr(L, "pt_debug_counter"):
             L.pt_debug_counter.argtypes = [C.c_int32]
             L.pt_debug_counter.restype = C.c_int64

@@ -14,10 +14,12 @@ wave-iteration the lanes trace one segment each of paths at mixed depths. Two qu
    jittered reflection leaves the surface; a wave pays max-over-lanes trips. Mean trips per
    specular lane against the wave's max.
 3. Last-ray rule: a path's last ray (segment depth - 1) that provably fails
-   every emitter leaf box (emit_reject, pt_math.h) is not traced; the bounce that made it
-   credits it and the lane takes the next path. Share of last rays and of rejected ones among
-   all rays, rays credited per wave-iteration, (lane, leaf) pairs and pair rounds per
-   iteration, each with and without the rule.
+   every emitter leaf box is not traced; the bounce that made it credits it and the lane takes
+   the next path. Two proofs: the sign rule (emit_reject, pt_math.h: origin outside the emitter
+   box E and direction pointing away, on some axis) and the slab rule (emit_slab_reject: E
+   itself fails the reference's slab test), and for comparison the last rays that do hit an
+   emitter. Share of last rays and of rejected ones among all rays, rays credited per
+   wave-iteration, (lane, leaf) pairs and pair rounds per iteration, without a rule and with each.
 
 usage: python scripts/wave_sim.py [--scene cornell|mcornell] [--rough R] [--paths N] [--depth D]
 """
@@ -179,20 +181,36 @@ def emit_reject(lo, hi, o, d):
     return (((o < lo[None]) & (d < 0) | (o > hi[None]) & (d > 0)) & (np.abs(d) < 2)).any(axis=1)
 
 
-def last_ray_rule(segs, nodes, tri_idx, mtype, depth):
-    """Per path: True when its last ray exists and the rule rejects it."""
+def emit_slab_reject(lo, hi, o, d):
+    """pt_math.h's slab predicate: E = [lo, hi] itself fails aabb.h:20-29 (no guard case occurs here:
+    the directions have no zero component)."""
+    if (lo > hi).any():
+        return np.ones(len(o), dtype=bool)
+    inv = 1.0 / d
+    t1, t2 = (lo[None] - o) * inv, (hi[None] - o) * inv
+    tmin, tmax = np.max(np.minimum(t1, t2), axis=1), np.min(np.maximum(t1, t2), axis=1)
+    return (tmax < 0) | (tmin > tmax)
+
+
+def last_ray_rule(segs, nodes, tri_idx, mtype, depth, tris):
+    """Per path: whether its last ray exists, the sign rule rejects it, the slab rule rejects it,
+    and it hits an emitter."""
     lo, hi = np.full(3, np.inf), np.full(3, -np.inf)
     for lb, rt, first, last in leaf_boxes(nodes):
         if any(mtype[int(tri_idx[i])] == EMIT for i in range(first, last + 1)):
             lo, hi = np.minimum(lo, lb), np.maximum(hi, rt)
     has = np.array([len(s) == depth and depth >= 2 for s in segs])
-    rej = np.zeros(len(segs), dtype=bool)
+    rej, slab, lit = (np.zeros(len(segs), dtype=bool) for _ in range(3))
     if has.any():
         idx = np.nonzero(has)[0]
         o = np.array([segs[i][-1][0] for i in idx])
         d = np.array([segs[i][-1][1] for i in idx])
         rej[idx] = emit_reject(lo, hi, o, d)
-    return has, rej
+        slab[idx] = emit_slab_reject(lo, hi, o, d)
+        hit, _ = intersect(tris, o, d)
+        lit[idx] = (hit >= 0) & (mtype[np.maximum(hit, 0)] == EMIT)
+    assert not (rej & ~slab).any() and not (slab & lit).any()  # sign => slab, and neither ends a lit path
+    return has, rej, slab, lit
 
 
 def pair_stats(its, leaves, credited):
@@ -269,19 +287,26 @@ def main():
             "trip_histogram": np.bincount(np.array(spec_lanes), minlength=8)[:12].tolist(),
         }
     # 3. the last-ray rule: the rejected last segments leave the paths, their rays stay credited
-    has, rej = last_ray_rule(segs, nodes, tri_idx, mtype, a.depth)
+    has, rej, slab, lit = last_ray_rule(segs, nodes, tri_idx, mtype, a.depth, tris)
     leaves = leaf_boxes(nodes)
     full = sum(len(o) for o, _, _ in its)
-    cut = [s[:-1] if r else s for s, r in zip(segs, rej)]
-    its_rule = simulate(cut, trips)
-    traced = sum(len(o) for o, _, _ in its_rule)
-    # rays credited in the simulated (steady-state) iterations: the traced ones and the early
-    # ends' share of them (the drain tail is cut from both runs)
+
+    def with_rule(r):
+        # rays credited in the simulated (steady-state) iterations: the traced ones and the early
+        # ends' share of them (the drain tail is cut from both runs)
+        its_rule = simulate([s[:-1] if x else s for s, x in zip(segs, r)], trips)
+        traced = sum(len(o) for o, _, _ in its_rule)
+        return pair_stats(its_rule, leaves, traced * nseg / (nseg - float(r.sum())))
+
     out["last_ray_rule"] = {
         "last_rays_over_all_rays": float(has.sum()) / nseg, "rejected_over_all_rays": float(rej.sum()) / nseg,
         "rejected_over_last_rays": float(rej.sum()) / max(1, int(has.sum())),
+        "slab_rejected_over_all_rays": float(slab.sum()) / nseg,
+        "slab_rejected_over_last_rays": float(slab.sum()) / max(1, int(has.sum())),
+        "last_rays_that_hit_an_emitter_over_all_rays": float(lit.sum()) / nseg,
         "without": pair_stats(its, leaves, full),
-        "with": pair_stats(its_rule, leaves, traced * nseg / (nseg - float(rej.sum()))),
+        "with": with_rule(rej),
+        "with_slab": with_rule(slab),
     }
     print(json.dumps(out, indent=1))
 
