@@ -14,6 +14,8 @@
  *   pt_bvh_trace_grad / pt_ctx_trace_grad: its exact gradient w.r.t. color and emit_color
  *   pt_ctx_render_aov                <- Camera::get_ray camera.h:63-73 + BVH::intersect + Triangle::normal
  *                                       triangle.h:45-49 (the first hit of a sample, per pixel)
+ *   pt_ctx_render_moments / pt_ctx_unconverged / pt_ctx_render_converge: the render's per-pixel
+ *                                       sample moments, their error estimate, rendering to a noise target
  *   pt_bvh_build                     <- BVH::build()  bvh.h:79-155 (find_best_axis 48-78)
  *   pt_camera_init                   <- Camera::Camera() camera.h:33-61
  *   pt_sample_seed                   <- rng.h:32 global LCG (stream policy, see below)
@@ -261,6 +263,72 @@ int pt_ctx_render(pt_ctx* ctx, const pt_camera* cam, const pt_params* params,
  * s_count (params->spp is ignored). Any other render on the context ends the sum. */
 int pt_ctx_render_progressive(pt_ctx* ctx, const pt_camera* cam, const pt_params* params, int32_t s_first,
                               int32_t s_count, float* out, int out_is_device, pt_stats* stats);
+
+/* ---- per-pixel sample moments, error estimates, rendering to a noise target ----
+ * r_s = the float32 radiance pt_ctx_render adds for sample s of a pixel and channel. Per pixel of
+ * the part and channel, in the layout of `out` (rows*W*3), every pointer optional (NULL = skipped):
+ *   sum    S = sum over s of (double)r_s, individually rounded double additions in sample order
+ *          from +0.0
+ *   sumsq  Q = sum over s of (double)r_s * (double)r_s (the product is exact in double), same order
+ *   sem    the standard error of the mean with n = the samples summed so far:
+ *          (float)sqrt(max(0, (Q - S*S/n) / (n - 1)) / n), evaluated in double; +inf for n < 2
+ * S and Q are defined bit for bit and do not depend on how the samples are cut into launches. */
+typedef struct pt_moments {
+    double* sum;
+    double* sumsq;
+    float*  sem;
+} pt_moments;
+
+/* pt_ctx_render_progressive that also keeps S and Q: adds samples [s_first, s_first + s_count) to
+ * the context's running MOMENTS sum. s_first == 0 starts one; otherwise the call must continue
+ * this context's running moments sum with the same camera, depth, seed and partition (else
+ * PT_E_ARG; a sum started by pt_ctx_render_progressive cannot be continued here, nor the other
+ * way round). Any other render on the context ends the sum; queries, pt_ctx_trace and
+ * pt_ctx_trace_grad leave it valid. `out` (optional) receives the running mean, bit-identical to
+ * pt_ctx_render with spp = s_first + s_count; `mom` (optional) the moments after this call.
+ * out_is_device covers `out` and the three pointers of `mom`. Every launch's slab is summed by a
+ * pass of its own (no fused accumulation), which keeps six doubles per pixel on the device. */
+int pt_ctx_render_moments(pt_ctx* ctx, const pt_camera* cam, const pt_params* params, int32_t s_first,
+                          int32_t s_count, float* out, const pt_moments* mom, int out_is_device, pt_stats* stats);
+
+/* Convergence count. With n samples summed, a channel is converged iff
+ *     n*Q - S*S  <=  (n-1) * t*t,   t = rel*|S| + abs*n        (n >= 2)
+ * which is sem <= rel*|mean| + abs with every division and the square root cleared away. It is
+ * evaluated in double, every operation rounded on its own, in this order: a = n*Q; b = S*S;
+ * l = a - b; t = rel*|S| + abs*n; r = (n-1)*(t*t); converged = l <= r (rel and abs widened from
+ * float). A pixel is converged iff its three channels are; n < 2: none is; a NaN makes the
+ * comparison false (unconverged). *count = the unconverged pixels; mask (optional, npix bytes):
+ * 1 for an unconverged pixel, else 0. A pixel whose samples so far are all +0 counts as converged
+ * (S = Q = 0): a minimum sample count is the guard. rel >= 0, abs >= 0, not both 0 (else PT_E_ARG). */
+/* On the host over the caller's arrays (npix*3 doubles each; no device needed). */
+int pt_moments_unconverged(const double* sum, const double* sumsq, int64_t npix, int32_t n, float rel, float abs,
+                           int64_t* count, uint8_t* mask);
+/* On the context's current moments sum (PT_E_ARG without one): the same count, by a device
+ * reduction; mask_is_device != 0: `mask` is a device pointer. */
+int pt_ctx_unconverged(pt_ctx* ctx, float rel, float abs, int64_t* count, uint8_t* mask, int mask_is_device);
+
+/* Render until the noise target is met. Round boundaries: n_0 = min_spp, then n_{k+1} =
+ * min(max_spp, n_k + step), or min(max_spp, 2 n_k) when step == 0. After each boundary the
+ * unconverged count is read back (8 bytes); the render stops at the first boundary whose count
+ * <= max_unconverged, or at max_spp. */
+typedef struct pt_converge {
+    float rel, abs;              /* the criterion above; rel >= 0, abs >= 0, not both 0 */
+    int32_t min_spp, max_spp;    /* 2 <= min_spp <= max_spp */
+    int32_t step;                /* samples per round after the first (>= 0); 0 = double */
+    int64_t max_unconverged;     /* stop when count <= this */
+} pt_converge;
+typedef struct pt_converge_stats {
+    int32_t spp, rounds;         /* samples per pixel rendered; boundaries evaluated */
+    int64_t unconverged;         /* the count at the last boundary */
+    uint64_t rays;               /* summed over the rounds, as the times below */
+    double kernel_ms, reduce_ms, total_ms;
+} pt_converge_stats;
+/* params->spp is ignored. The image (`out`, optional) is bit-identical to pt_ctx_render at spp =
+ * cs->spp; `mom` (optional) as pt_ctx_render_moments. The moments sum stays valid afterwards, so
+ * pt_ctx_render_moments can continue it from cs->spp. PT_E_RUNAWAY is reported as by
+ * pt_ctx_render (the rounds still run and the results are written). */
+int pt_ctx_render_converge(pt_ctx* ctx, const pt_camera* cam, const pt_params* params, const pt_converge* conv,
+                           float* out, const pt_moments* mom, int out_is_device, pt_converge_stats* cs);
 
 /* pt_ctx_render followed by gamma_correct + save_png quantisation on the device
  * (image.h:41-55): out receives rows*W*3 bytes of this part (row order as pt_ctx_render;

@@ -26,6 +26,7 @@
 
 #include "pt_internal.h"
 #include "pt_math.h"
+#include "pt_moments.h"
 
 namespace pt {
 
@@ -1760,6 +1761,25 @@ int pt_rgb8_thresholds(float gamma, float* thr, int32_t* neg_mode) {
         thr[k - 1] = u2f(hi);
     }
     if (neg_mode) *neg_mode = (floorf(inv) != inv) ? 0 : (fmodf(inv, 2.0f) == 1.0f ? 1 : 2);
+    return PT_OK;
+}
+
+// The convergence count of per-pixel sample moments on the host (the criterion: pt_moments.h).
+// Tolerances: both non-negative (which a NaN is not), not both 0.
+int pt_moments_unconverged(const double* sum, const double* sumsq, int64_t npix, int32_t n, float rel, float abs,
+                           int64_t* count, uint8_t* mask) {
+    if (!count) return set_error(PT_E_ARG, "pt_moments_unconverged: count is NULL");
+    if (npix < 0 || (npix > 0 && (!sum || !sumsq))) return set_error(PT_E_ARG, "pt_moments_unconverged: bad arrays");
+    if (!(rel >= 0.0f) || !(abs >= 0.0f) || (rel == 0.0f && abs == 0.0f))
+        return set_error(PT_E_ARG, "pt_moments_unconverged: rel and abs must be >= 0 and not both 0");
+    const double drel = (double)rel, dabs = (double)abs;
+    int64_t c = 0;
+    for (int64_t q = 0; q < npix; q++) {
+        const bool un = moments_pixel_unconverged(sum + 3 * q, sumsq + 3 * q, n, drel, dabs);
+        c += un ? 1 : 0;
+        if (mask) mask[q] = un ? 1 : 0;
+    }
+    *count = c;
     return PT_OK;
 }
 

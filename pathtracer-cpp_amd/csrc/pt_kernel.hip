@@ -6,6 +6,9 @@
 //                                 boxes fold), compiled in the background from
 //                                 pt_ctx_set_scene on (rtc_job, pt_rtc.hip)
 //   pt_accumulate_kernel          in-order per-pixel accumulation + /spp
+//   pt_accumulate_moments_kernel  the same with the per-pixel double sums S and Q (pt_moments)
+//   pt_moments_sem_kernel         their standard error of the mean
+//   pt_unconverged_kernel         the convergence count of the moments (ballot + one atomic per block)
 //   pt_math_kernel                device copies of the math primitives (test hook)
 #include <hip/hip_runtime.h>
 
@@ -29,6 +32,7 @@
 #include "pt_grad.h"
 #include "pt_hip_debug.h"
 #include "pt_launch.h"
+#include "pt_moments.h"
 #include "pt_rtc.h"
 #include "pt_trace.h"
 
@@ -76,8 +80,31 @@ static TraceKernel wide_kernel(int width, int fmt, bool lds_mats) {
                              : wide_kernel_t<4, kWideByte>(lds_mats);
 }
 
+// A pixel's running sums as slab_walk's accumulator (pt_trace.h) in a moments render: the image's
+// float32 sum (SumF32's) and, per channel beside it, S = sum of (double)r and Q = sum of
+// (double)r * (double)r (include/pt_hip.h: pt_moments; the product of two floats is exact in
+// double, every addition is rounded on its own). A +0 record (a slot the parallel walk pads
+// with) changes none of them.
+struct MomentSums {
+    float &x, &y, &z;
+    double sx, sy, sz, qx, qy, qz;
+    __device__ __forceinline__ void add(const float3 v) {
+        x += v.x;
+        y += v.y;
+        z += v.z;
+        const double dx = (double)v.x, dy = (double)v.y, dz = (double)v.z;
+        sx += dx;
+        sy += dy;
+        sz += dz;
+        qx += dx * dx;
+        qy += dy * dy;
+        qz += dz * dz;
+    }
+};
+
 // Running per-pixel sum in sample order (image.h:27-31 via render.h:84), then /spp
-// (image.h:37-40) on the last batch; output interleaved RGB rows of this part.
+// (image.h:37-40) on the last batch; output interleaved RGB rows of this part. The order of the
+// sum is slab_walk<true>'s (pt_trace.h): dense records, or a flagged slab's flagged ones.
 __global__ __launch_bounds__(kBlock) void pt_accumulate_kernel(const float* __restrict__ radiance,
                                                                float* __restrict__ accum, float* __restrict__ out,
                                                                int npix, int s_count, int first, int last,
@@ -88,31 +115,8 @@ __global__ __launch_bounds__(kBlock) void pt_accumulate_kernel(const float* __re
     float x = first ? 0.0f : accum[q];
     float y = first ? 0.0f : accum[npix + q];
     float z = first ? 0.0f : accum[2 * (size_t)npix + q];
-    if (flags) {
-        // a flagged slab (TraceArgs::flags): only the records of paths that did not end dark
-        slab_sum<true>(radiance, flags, flags_pm, s_count, (uint32_t)q, (uint32_t)npix, x, y, z);
-    } else {
-        // 8 samples' loads in flight per step, added in sample order: a part of few pixels
-        // (one rank's rows at 8 GPUs: 131k threads) is latency-bound with one sample per step
-        int sl = 0;
-        for (; sl + 8 <= s_count; sl += 8) {
-            float3 v[8];
-#pragma unroll
-            for (int j = 0; j < 8; j++) v[j] = slab_at(radiance, (size_t)(sl + j), (uint32_t)q, (uint32_t)npix);
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                x += v[j].x;
-                y += v[j].y;
-                z += v[j].z;
-            }
-        }
-        for (; sl < s_count; sl++) {
-            const float3 v = slab_at(radiance, (size_t)sl, (uint32_t)q, (uint32_t)npix);
-            x += v.x;
-            y += v.y;
-            z += v.z;
-        }
-    }
+    SumF32 a{x, y, z};
+    slab_walk<true>(radiance, flags, flags_pm, s_count, (uint32_t)q, (uint32_t)npix, a);
     if (last) {
         out[3 * (size_t)q] = x / spp;
         out[3 * (size_t)q + 1] = y / spp;
@@ -122,6 +126,90 @@ __global__ __launch_bounds__(kBlock) void pt_accumulate_kernel(const float* __re
         accum[q] = x;
         accum[npix + q] = y;
         accum[2 * (size_t)npix + q] = z;
+    }
+}
+
+// pt_accumulate_kernel for a moments render (pt_ctx_render_moments): the same walk, the same
+// image, and the context's six doubles per pixel continued in `mom`: S at [3 q + c], Q at
+// [3 npix + 3 q + c] (the layout of `out`). The float32 sum always stays.
+__global__ __launch_bounds__(kBlock) void pt_accumulate_moments_kernel(const float* __restrict__ radiance,
+                                                                       float* __restrict__ accum,
+                                                                       float* __restrict__ out, double* __restrict__ mom,
+                                                                       int npix, int s_count, int first, int last,
+                                                                       float spp, const uint32_t* __restrict__ flags,
+                                                                       int flags_pm) {
+    const int q = blockIdx.x * kBlock + threadIdx.x;
+    if (q >= npix) return;
+    float x = first ? 0.0f : accum[q];
+    float y = first ? 0.0f : accum[npix + q];
+    float z = first ? 0.0f : accum[2 * (size_t)npix + q];
+    double* S = mom + 3 * (size_t)q;
+    double* Q = S + 3 * (size_t)npix;
+    MomentSums a{x, y, z, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (!first) {
+        a.sx = S[0];
+        a.sy = S[1];
+        a.sz = S[2];
+        a.qx = Q[0];
+        a.qy = Q[1];
+        a.qz = Q[2];
+    }
+    slab_walk<true>(radiance, flags, flags_pm, s_count, (uint32_t)q, (uint32_t)npix, a);
+    if (last) {
+        out[3 * (size_t)q] = x / spp;
+        out[3 * (size_t)q + 1] = y / spp;
+        out[3 * (size_t)q + 2] = z / spp;
+    }
+    accum[q] = x;
+    accum[npix + q] = y;
+    accum[2 * (size_t)npix + q] = z;
+    S[0] = a.sx;
+    S[1] = a.sy;
+    S[2] = a.sz;
+    Q[0] = a.qx;
+    Q[1] = a.qy;
+    Q[2] = a.qz;
+}
+
+// The standard error of the mean of n samples from the moments (one thread per pixel and channel):
+// sqrt(max(0, (Q - S*S/n) / (n-1)) / n) in double, rounded to float; +inf for n < 2. A NaN stays.
+__global__ __launch_bounds__(kBlock) void pt_moments_sem_kernel(const double* __restrict__ mom, size_t nval, int n,
+                                                                float* __restrict__ sem) {
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= nval) return;
+    if (n < 2) {
+        sem[i] = __builtin_inff();
+        return;
+    }
+    const double S = mom[i], Q = mom[nval + i], dn = (double)n;
+    double var = (Q - S * S / dn) / (dn - 1.0);
+    if (var < 0.0) var = 0.0;
+    sem[i] = (float)sqrt(var / dn);
+}
+
+// The unconverged pixels of the moments (the criterion: pt_moments.h), one pixel per lane: a wave
+// counts by ballot and popcount, a block adds its waves' counts with one atomic. mask (optional):
+// one byte per pixel, 1 = unconverged.
+__global__ __launch_bounds__(kBlock) void pt_unconverged_kernel(const double* __restrict__ mom, int npix, int n,
+                                                                double rel, double abs_tol,
+                                                                unsigned long long* __restrict__ count,
+                                                                uint8_t* __restrict__ mask) {
+    __shared__ unsigned int wave_count[kBlock / kWave];
+    const int q = blockIdx.x * kBlock + threadIdx.x;
+    bool un = false;
+    if (q < npix) {
+        const double* S = mom + 3 * (size_t)q;
+        un = moments_pixel_unconverged(S, S + 3 * (size_t)npix, n, rel, abs_tol);
+        if (mask) mask[q] = un ? 1 : 0;
+    }
+    const unsigned long long b = __ballot(un);
+    if ((threadIdx.x & (kWave - 1)) == 0) wave_count[threadIdx.x / kWave] = (unsigned int)__popcll(b);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned int t = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / kWave; w++) t += wave_count[w];
+        if (t) atomicAdd(count, (unsigned long long)t);
     }
 }
 
@@ -320,9 +408,19 @@ struct pt_ctx {
     size_t gmats_f4 = 0;
     float* d_gbuf = nullptr;                 // staging of a host-pointer call's override rows and grad_rgb
     size_t gbuf_floats = 0;
-    // progressive rendering: d_accum holds the running sum of prog_spp samples
+    // sample moments (pt_ctx_render_moments): S and Q, 6 doubles per pixel (48 x npix bytes), made on
+    // first use and released with the slabs; the unconverged count; staging of a host-pointer sem
+    double* d_mom = nullptr;
+    size_t mom_doubles = 0;
+    unsigned long long* d_mcount = nullptr;
+    float* d_sem = nullptr;
+    size_t sem_floats = 0;
+    // progressive rendering: d_accum holds the running sum of prog_spp samples; prog_moments: the
+    // sum is a moments sum (d_mom continues with it, over prog_npix pixels)
     bool prog_valid = false;
+    bool prog_moments = false;
     int prog_spp = 0;
+    int prog_npix = 0;
     pt_camera prog_cam{};
     pt_params prog_prm{};
     hipFunction_t rtc_flat = nullptr;        // scene-specialised flat kernel (hipRTC), if built
@@ -392,7 +490,8 @@ int64_t pt::kernel_counter(int which) { return which == 0 ? g_ctx_created.load()
 
 // The context's radiance slabs and their flags (the largest buffers: up to half the free HBM)
 // back to the device; the next render allocates them again. The scene, accumulation and
-// output buffers stay (pt_multi.hip: cached multi-device contexts after each render).
+// output buffers stay (pt_multi.hip: cached multi-device contexts after each render). The
+// moments buffer goes too, and a running moments sum ends with it.
 int pt::ctx_release_slabs(pt_ctx* c) {
     if (!c) return PT_OK;
     if (int rc = ctx_ready(c)) return rc;
@@ -404,6 +503,10 @@ int pt::ctx_release_slabs(pt_ctx* c) {
     c->radiance_floats = 0;
     c->d_flags = nullptr;
     c->flags_words = 0;
+    if (c->d_mom) (void)hipFree(c->d_mom);
+    c->d_mom = nullptr;
+    c->mom_doubles = 0;
+    if (c->prog_moments) c->prog_valid = false;
     return PT_OK;
 }
 
@@ -478,6 +581,7 @@ struct RenderPlan {
     // batching (plan_batch)
     int batch = 0, per_item = 1, tail = 0;
     bool fused = false, flagged = false;
+    bool moments = false;  // a moments render: every slab summed by pt_accumulate_moments_kernel (never fused)
     int flags_pm = 0;
     size_t slab_floats = 0, slab_words = 0;  // one radiance slab and its flag bits
     // kernel family and its LDS
@@ -526,7 +630,8 @@ void plan_batch(const pt_ctx* c, const pt_params* prm, RenderPlan& P) {
     // needs pt_accumulate_kernel between trace launches. Two slabs alternate; an automatic
     // batch is halved so both fit the budget of one. PT_FUSED_ACC=0 (test hook): the
     // separate pass after every launch.
-    bool fused = (spp - s_lo) > batch && !hook_off("PT_FUSED_ACC");
+    // A moments render (P.moments) takes that separate pass too: the double sums live in it.
+    bool fused = (spp - s_lo) > batch && !hook_off("PT_FUSED_ACC") && !P.moments;
     if (fused && prm->batch_spp <= 0 && !halved) batch = std::max(1, (batch + 1) / 2);
     // an explicit batch keeps its size: fusion (two slabs) only when both fit the budget (read
     // here, before render_buffers grows the sum, staging and stack buffers: the free HBM it
@@ -553,9 +658,12 @@ void plan_batch(const pt_ctx* c, const pt_params* prm, RenderPlan& P) {
     // for frames of several launches, whose slabs the trace kernels sum (fused accumulation):
     // headline whole job +0.7 %, config 5 +0.6 %; sample-major (round 5) for one-launch frames
     // (an 8-GPU share), whose trace kernel measured 1 % slower with the other layout
-    // (profiles/r06_flags). PT_FLAGS_PM=0 / 1 (test hook) forces one.
+    // (profiles/r06_flags). A moments render of several launches sums every slab in the separate
+    // pass and takes the pixel-major words too: that pass 10.7 -> 3.2 ms per 8192-spp Cornell frame,
+    // the trace kernels the same (profiles/moments). PT_FLAGS_PM=0 / 1 (test hook) forces one.
     const char* pm_env = hook_env("PT_FLAGS_PM");
-    P.flags_pm = (pm_env && *pm_env) ? (*pm_env == '1' ? 1 : 0) : (fused ? 1 : 0);
+    const bool several = fused || (P.moments && (spp - s_lo) > batch);
+    P.flags_pm = (pm_env && *pm_env) ? (*pm_env == '1' ? 1 : 0) : (several ? 1 : 0);
     P.slab_words = P.flags_pm ? ((size_t)batch + 31) / 32 * npix : ((size_t)batch * npix + 31) / 32;
 }
 
@@ -655,8 +763,9 @@ void plan_tree(const pt_ctx* c, RenderPlan& P) {
 
 // Everything a render decides before it allocates or launches: batch, kernel family, LDS
 // layout, kernel and blocks per CU.
-int plan_render(pt_ctx* c, const PartShape& shape, const pt_params* prm, int s_lo, int spp, RenderPlan& P) {
+int plan_render(pt_ctx* c, const PartShape& shape, const pt_params* prm, int s_lo, int spp, bool moments, RenderPlan& P) {
     P.shape = shape;
+    P.moments = moments;
     P.s_lo = s_lo;
     P.spp = spp;
     P.rec = std::max(1, prm->depth - 1);
@@ -697,12 +806,13 @@ int plan_render(pt_ctx* c, const PartShape& shape, const pt_params* prm, int s_l
     return PT_OK;
 }
 
-// The running sum, the output staging, the radiance slabs with their flag bits, and the exact
-// walk's stacks.
+// The running sum, the output staging, the radiance slabs with their flag bits, the exact
+// walk's stacks, and a moments render's double sums.
 int render_buffers(pt_ctx* c, const RenderPlan& P, bool out_is_device) {
     const size_t npix = (size_t)P.shape.npix;
     int rc;
     if ((rc = ensure(&c->d_accum, &c->accum_floats, 3 * npix))) return rc;
+    if (P.moments && (rc = ensure(&c->d_mom, &c->mom_doubles, 6 * npix))) return rc;
     if (!out_is_device && (rc = ensure(&c->d_out, &c->out_floats, 3 * npix))) return rc;
     if (P.wide || P.flat) {
         // a compile still running may switch this render to the hipRTC kernel, whose
@@ -918,7 +1028,11 @@ int launch_batch(pt_ctx* c, RenderPlan& P, TraceArgs& A, int b, int s0, int sc, 
         hipLaunchKernelGGL(P.kern, dim3(grid), dim3(kBlock), P.lds_bytes, c->stream, A);
     }
     (void)hipEventRecord(e[1], c->stream);
-    if (!P.fused || s0 + sc >= P.spp)  // fused: only the last batch (the others are summed by the next launch)
+    if (P.moments)
+        hipLaunchKernelGGL(pt_accumulate_moments_kernel, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream,
+                           slab, c->d_accum, dst, c->d_mom, npix, sc, s0 == 0 ? 1 : 0, s0 + sc >= P.spp ? 1 : 0,
+                           (float)P.spp, A.flags, P.flags_pm);
+    else if (!P.fused || s0 + sc >= P.spp)  // fused: only the last batch (the others are summed by the next launch)
         hipLaunchKernelGGL(pt_accumulate_kernel, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, slab,
                            c->d_accum, dst, npix, sc, s0 == 0 ? 1 : 0, s0 + sc >= P.spp ? 1 : 0, keep, (float)P.spp, A.flags,
                            P.flags_pm);
@@ -1010,7 +1124,7 @@ int finish_render(pt_ctx* c, const RenderPlan& P, const TraceArgs& A, const pt_p
     }
     unsigned long long h_ctr[5] = {0, 0, 0, 0, 0};
     hipError_t e = hipMemcpyAsync(h_ctr, c->d_ctr, sizeof(h_ctr), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && !out_is_device)
+    if (e == hipSuccess && !out_is_device && out)  // a moments render may want no image
         e = hipMemcpyAsync(out, dst, 3 * (size_t)npix * sizeof(float), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return set_error(PT_E_HIP, "render failed: %s", hipGetErrorString(e));
@@ -1052,10 +1166,12 @@ int finish_render(pt_ctx* c, const RenderPlan& P, const TraceArgs& A, const pt_p
 
 // Samples [s_lo, s_hi) of this part added to the running sum (a new sum when s_lo == 0),
 // the image = sum / s_hi written to `out`; keep: the sum stays in d_accum (progressive).
+// moments: the double sums S and Q in d_mom are started or continued with it, `out` is optional
+// (NULL: the image stays in the staging buffer d_out) and the sum always stays.
 int render_range(pt_ctx* c, const pt_camera* cam, const pt_params* prm, int s_lo, int s_hi, int keep, float* out,
-                 int out_is_device, pt_stats* stats) {
+                 int out_is_device, pt_stats* stats, bool moments = false) {
     const auto t_start = std::chrono::steady_clock::now();
-    if (!c || !cam || !prm || !out) return set_error(PT_E_ARG, "pt_ctx_render: NULL argument");
+    if (!c || !cam || !prm || (!out && !moments)) return set_error(PT_E_ARG, "pt_ctx_render: NULL argument");
     if (s_lo < 0 || s_hi < s_lo) return set_error(PT_E_ARG, "bad sample range [%d, %d)", s_lo, s_hi);
     if (!c->have_scene) return set_error(PT_E_ARG, "pt_ctx_render: no scene set");
     int rc;
@@ -1065,9 +1181,10 @@ int render_range(pt_ctx* c, const pt_camera* cam, const pt_params* prm, int s_lo
     HIP_TRY(hipSetDevice(c->device));
 
     RenderPlan P;
-    if ((rc = plan_render(c, shape, prm, s_lo, s_hi, P))) return rc;
-    if ((rc = render_buffers(c, P, out_is_device))) return rc;
-    float* dst = out_is_device ? out : c->d_out;
+    if ((rc = plan_render(c, shape, prm, s_lo, s_hi, moments, P))) return rc;
+    const bool to_device = out_is_device && out;
+    if ((rc = render_buffers(c, P, to_device))) return rc;
+    float* dst = to_device ? out : c->d_out;
     TraceArgs A;
     if ((rc = fill_trace_args(c, P, cam, prm, A))) return rc;
 
@@ -1080,8 +1197,12 @@ int render_range(pt_ctx* c, const pt_camera* cam, const pt_params* prm, int s_lo
     const int npix = shape.npix, spp = s_hi;
     if (s_lo == spp && npix > 0) {
         // No samples: the reference divides the zero image by 0 (render.h:97).
-        hipLaunchKernelGGL(pt_accumulate_kernel, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream,
-                           c->d_radiance, c->d_accum, dst, npix, 0, s_lo == 0 ? 1 : 0, 1, keep, (float)spp, nullptr, 0);
+        if (moments)
+            hipLaunchKernelGGL(pt_accumulate_moments_kernel, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream,
+                               c->d_radiance, c->d_accum, dst, c->d_mom, npix, 0, s_lo == 0 ? 1 : 0, 1, (float)spp, nullptr, 0);
+        else
+            hipLaunchKernelGGL(pt_accumulate_kernel, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream,
+                               c->d_radiance, c->d_accum, dst, npix, 0, s_lo == 0 ? 1 : 0, 1, keep, (float)spp, nullptr, 0);
     }
     RenderEvents events;
     LaunchLog log;
@@ -1092,7 +1213,109 @@ int render_range(pt_ctx* c, const pt_camera* cam, const pt_params* prm, int s_lo
         prev_s0 = s0;
         prev_sc = sc;
     }
-    return finish_render(c, P, A, prm, events, log, out, dst, out_is_device != 0, t_start, stats);
+    return finish_render(c, P, A, prm, events, log, out, dst, to_device, t_start, stats);
+}
+
+// Whether samples from s_first on continue the context's running sum of that kind (moments or
+// plain progressive): the same camera, depth, seed and partition.
+bool continues_sum(const pt_ctx* c, bool moments, const pt_camera* cam, const pt_params* prm, int s_first) {
+    return c->prog_valid && c->prog_moments == moments && c->prog_spp == s_first &&
+           memcmp(&c->prog_cam, cam, sizeof(pt_camera)) == 0 && c->prog_prm.depth == prm->depth &&
+           c->prog_prm.seed == prm->seed && c->prog_prm.part_index == prm->part_index &&
+           c->prog_prm.part_count == prm->part_count && c->prog_prm.band_rows == prm->band_rows;
+}
+
+void keep_sum(pt_ctx* c, bool moments, const pt_camera* cam, const pt_params* prm, int spp, int npix) {
+    c->prog_valid = true;
+    c->prog_moments = moments;
+    c->prog_spp = spp;
+    c->prog_npix = npix;
+    c->prog_cam = *cam;
+    c->prog_prm = *prm;
+}
+
+bool tolerances_ok(float rel, float abs_tol) { return rel >= 0.0f && abs_tol >= 0.0f && !(rel == 0.0f && abs_tol == 0.0f); }
+
+// Samples [s_first, s_first + s_count) added to the context's moments sum (the checks and the
+// bookkeeping of pt_ctx_render_moments without its export). A runaway render still leaves a
+// valid sum: its code is returned after the bookkeeping.
+int moments_range(pt_ctx* c, const pt_camera* cam, const pt_params* prm, int32_t s_first, int32_t s_count, float* out,
+                  int out_is_device, pt_stats* stats) {
+    if (!c || !cam || !prm) return set_error(PT_E_ARG, "pt_ctx_render_moments: NULL argument");
+    if (s_first < 0 || s_count < 0 || (long long)s_first + s_count > 0x7fffffffll)
+        return set_error(PT_E_ARG, "pt_ctx_render_moments: bad sample range");
+    if (s_first > 0 && !continues_sum(c, true, cam, prm, s_first))
+        return set_error(PT_E_ARG,
+                         "moments render: samples from %d do not continue this context's running moments sum "
+                         "(%d samples, a progressive sum, or another camera / parameters)",
+                         s_first, c->prog_valid && c->prog_moments ? c->prog_spp : 0);
+    c->prog_valid = false;
+    PartShape shape;
+    if (int rc = part_shape(cam, prm, PT_MAX_DEPTH, &shape)) return rc;
+    const int rc = render_range(c, cam, prm, s_first, s_first + s_count, 1, out, out_is_device, stats, true);
+    if (rc && rc != PT_E_RUNAWAY) return rc;
+    keep_sum(c, true, cam, prm, s_first + s_count, shape.npix);
+    return rc;
+}
+
+// The context's moments to the caller's arrays (device or host pointers): S and Q are copies of
+// d_mom's halves, sem is computed from them. Synchronous.
+int moments_export(pt_ctx* c, const pt_moments* mom, int is_device) {
+    const size_t nval = 3 * (size_t)c->prog_npix;
+    if (!mom || nval == 0) return PT_OK;
+    const hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (mom->sum) HIP_TRY(hipMemcpyAsync(mom->sum, c->d_mom, nval * sizeof(double), kind, c->stream));
+    if (mom->sumsq) HIP_TRY(hipMemcpyAsync(mom->sumsq, c->d_mom + nval, nval * sizeof(double), kind, c->stream));
+    if (mom->sem) {
+        if (!is_device)
+            if (int rc = ensure(&c->d_sem, &c->sem_floats, nval)) return rc;
+        float* dst = is_device ? mom->sem : c->d_sem;
+        hipLaunchKernelGGL(pt_moments_sem_kernel, dim3((unsigned)((nval + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
+                           c->d_mom, nval, c->prog_spp, dst);
+        if (!is_device) HIP_TRY(hipMemcpyAsync(mom->sem, dst, nval * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+// The unconverged pixels of the context's moments sum (pt_unconverged_kernel); ms (optional): the
+// kernel's duration is added.
+int unconverged_count(pt_ctx* c, float rel, float abs_tol, int64_t* count, uint8_t* mask, int mask_is_device, double* ms) {
+    const int npix = c->prog_npix;
+    *count = 0;
+    if (npix <= 0) return PT_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->d_mcount) HIP_TRY(hipMalloc((void**)&c->d_mcount, sizeof(unsigned long long)));
+    uint8_t* d_mask = mask;
+    if (mask && !mask_is_device) {
+        if (int rc = ensure(&c->d_rgb8, &c->rgb8_bytes, (size_t)npix)) return rc;  // the 8-bit staging buffer
+        d_mask = c->d_rgb8;
+    }
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (ms && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) {
+        if (e0) (void)hipEventDestroy(e0);
+        return set_error(PT_E_HIP, "hipEventCreate failed");
+    }
+    unsigned long long h = 0;
+    hipError_t e = hipMemsetAsync(c->d_mcount, 0, sizeof(unsigned long long), c->stream);
+    if (ms) (void)hipEventRecord(e0, c->stream);
+    hipLaunchKernelGGL(pt_unconverged_kernel, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->d_mom, npix,
+                       c->prog_spp, (double)rel, (double)abs_tol, c->d_mcount, d_mask);
+    if (ms) (void)hipEventRecord(e1, c->stream);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(&h, c->d_mcount, sizeof(h), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && mask && !mask_is_device)
+        e = hipMemcpyAsync(mask, d_mask, (size_t)npix, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (ms) {
+        float t = 0;
+        if (e == hipSuccess && hipEventElapsedTime(&t, e0, e1) == hipSuccess) *ms += t;
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+    }
+    if (e != hipSuccess) return set_error(PT_E_HIP, "convergence count failed: %s", hipGetErrorString(e));
+    *count = (int64_t)h;
+    return PT_OK;
 }
 
 }  // namespace
@@ -1183,7 +1406,7 @@ void pt_ctx_destroy(pt_ctx* c) {
                     (void*)c->d_accum, (void*)c->d_out, (void*)c->d_ctr, (void*)c->d_stamps, (void*)c->d_rgb8, (void*)c->d_thr, (void*)c->d_xstack,
                     (void*)c->d_rank_tri, (void*)c->d_qstack, (void*)c->d_qbuf, (void*)c->d_qhits,
                     (void*)c->d_tslab, (void*)c->d_trec, (void*)c->d_tbuf, (void*)c->d_tstates, (void*)c->d_tctr,
-                    (void*)c->d_gtab, (void*)c->d_gmats, (void*)c->d_gbuf})
+                    (void*)c->d_gtab, (void*)c->d_gmats, (void*)c->d_gbuf, (void*)c->d_mom, (void*)c->d_mcount, (void*)c->d_sem})
         if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -1321,24 +1544,70 @@ int pt_ctx_render_progressive(pt_ctx* c, const pt_camera* cam, const pt_params* 
     if (!c || !cam || !prm) return set_error(PT_E_ARG, "pt_ctx_render_progressive: NULL argument");
     if (s_first < 0 || s_count < 0 || (long long)s_first + s_count > 0x7fffffffll)
         return set_error(PT_E_ARG, "pt_ctx_render_progressive: bad sample range");
-    if (s_first > 0) {
-        const bool same = c->prog_valid && c->prog_spp == s_first && memcmp(&c->prog_cam, cam, sizeof(pt_camera)) == 0 &&
-                          c->prog_prm.depth == prm->depth && c->prog_prm.seed == prm->seed &&
-                          c->prog_prm.part_index == prm->part_index && c->prog_prm.part_count == prm->part_count &&
-                          c->prog_prm.band_rows == prm->band_rows;
-        if (!same)
-            return set_error(PT_E_ARG,
-                             "progressive render: samples from %d do not continue this context's running sum "
-                             "(%d samples, or another camera / parameters)",
-                             s_first, c->prog_valid ? c->prog_spp : 0);
-    }
+    if (s_first > 0 && !continues_sum(c, false, cam, prm, s_first))
+        return set_error(PT_E_ARG,
+                         "progressive render: samples from %d do not continue this context's running sum "
+                         "(%d samples, a moments sum, or another camera / parameters)",
+                         s_first, c->prog_valid && !c->prog_moments ? c->prog_spp : 0);
     c->prog_valid = false;
     const int rc = render_range(c, cam, prm, s_first, s_first + s_count, 1, out, out_is_device, stats);
     if (rc) return rc;
-    c->prog_valid = true;
-    c->prog_spp = s_first + s_count;
-    c->prog_cam = *cam;
-    c->prog_prm = *prm;
+    keep_sum(c, false, cam, prm, s_first + s_count, 0);
+    return PT_OK;
+}
+
+int pt_ctx_render_moments(pt_ctx* c, const pt_camera* cam, const pt_params* prm, int32_t s_first, int32_t s_count,
+                          float* out, const pt_moments* mom, int out_is_device, pt_stats* stats) {
+    const int rc = moments_range(c, cam, prm, s_first, s_count, out, out_is_device, stats);
+    if (rc && rc != PT_E_RUNAWAY) return rc;
+    if (int xrc = moments_export(c, mom, out_is_device)) return xrc;
+    return rc;
+}
+
+int pt_ctx_unconverged(pt_ctx* c, float rel, float abs_tol, int64_t* count, uint8_t* mask, int mask_is_device) {
+    if (!c || !count) return set_error(PT_E_ARG, "pt_ctx_unconverged: NULL argument");
+    if (!tolerances_ok(rel, abs_tol))
+        return set_error(PT_E_ARG, "pt_ctx_unconverged: rel and abs must be >= 0 and not both 0");
+    if (!c->prog_valid || !c->prog_moments)
+        return set_error(PT_E_ARG, "pt_ctx_unconverged: the context has no running moments sum");
+    return unconverged_count(c, rel, abs_tol, count, mask, mask_is_device, nullptr);
+}
+
+int pt_ctx_render_converge(pt_ctx* c, const pt_camera* cam, const pt_params* prm, const pt_converge* cv, float* out,
+                           const pt_moments* mom, int out_is_device, pt_converge_stats* cs) {
+    const auto t_start = std::chrono::steady_clock::now();
+    if (!c || !cam || !prm || !cv) return set_error(PT_E_ARG, "pt_ctx_render_converge: NULL argument");
+    if (!tolerances_ok(cv->rel, cv->abs))
+        return set_error(PT_E_ARG, "pt_ctx_render_converge: rel and abs must be >= 0 and not both 0");
+    if (cv->min_spp < 2 || cv->max_spp < cv->min_spp || cv->step < 0 || cv->max_unconverged < 0)
+        return set_error(PT_E_ARG, "pt_ctx_render_converge: needs 2 <= min_spp <= max_spp, step >= 0, max_unconverged >= 0");
+    pt_converge_stats S{};
+    int runaway = PT_OK;
+    // rounds on a device image write it in place; a host image is copied once, after the last
+    for (int32_t done = 0, n = cv->min_spp;;) {
+        pt_stats st{};
+        const int rc = moments_range(c, cam, prm, done, n - done, out_is_device ? out : nullptr, out_is_device, &st);
+        if (rc && rc != PT_E_RUNAWAY) return rc;
+        if (rc) runaway = rc;
+        S.rays += st.rays;
+        S.kernel_ms += st.kernel_ms;
+        S.reduce_ms += st.reduce_ms;
+        if (int urc = unconverged_count(c, cv->rel, cv->abs, &S.unconverged, nullptr, 0, &S.reduce_ms)) return urc;
+        S.rounds++;
+        S.spp = done = n;
+        if (S.unconverged <= cv->max_unconverged || n >= cv->max_spp) break;
+        const int64_t next = cv->step > 0 ? (int64_t)n + cv->step : 2 * (int64_t)n;
+        n = (int32_t)std::min<int64_t>(next, cv->max_spp);
+    }
+    if (out && !out_is_device && c->prog_npix > 0) {
+        HIP_TRY(hipMemcpyAsync(out, c->d_out, 3 * (size_t)c->prog_npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    if (int xrc = moments_export(c, mom, out_is_device)) return xrc;
+    S.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    if (cs) *cs = S;
+    if (runaway)
+        return set_error(PT_E_RUNAWAY, "specular rejection loops hit the %d-iteration bound during the rounds", kMaxSpecularIters);
     return PT_OK;
 }
 

@@ -1469,17 +1469,19 @@ __device__ __forceinline__ size_t flag_word(uint32_t s, uint32_t q, uint32_t npi
     return (size_t)(s >> 5) * npix + q;
 }
 
-// Pixel q's samples [0, n) of a slab added to (x, y, z) in sample order (image.h:27-31: sum =
-// sum + sample); with flags, only the flagged records (the others are +0, §TraceArgs::flags).
+// Pixel q's samples [0, n) of a slab handed to acc.add(float3) in sample order (image.h:27-31:
+// sum = sum + sample; the one statement of that order: SumF32 below is the image's running sum,
+// pt_kernel.hip's moments accumulator adds the double sums beside it); with flags, only the
+// flagged records (the others are +0 and were never stored, §TraceArgs::flags).
 // Pixel-major bits (pm): one flag word per 32 samples, then its set bits' records read and
 // added in order; kParallel (the separate pass, pt_accumulate_kernel: a frame of few pixels —
 // one rank's share — is latency-bound there) loads 8 words and up to 8 records at once.
 // Sample-major bits: kDepth samples' bits gathered into a mask (one load each), then the set
 // ones' records read and added in order (kParallel: 32 samples, all their records at once;
 // inside the trace kernels, whose registers are spoken for: 8, one record at a time).
-template <bool kParallel = false>
-__device__ __forceinline__ void slab_sum(const float* __restrict__ src, const uint32_t* __restrict__ flags, int pm,
-                                         int n, uint32_t q, uint32_t npix, float& x, float& y, float& z) {
+template <bool kParallel = false, class Acc>
+__device__ __forceinline__ void slab_walk(const float* __restrict__ src, const uint32_t* __restrict__ flags, int pm,
+                                          int n, uint32_t q, uint32_t npix, Acc& acc) {
     int s = 0;
     if (flags && pm) {
         const int nw = (n + 31) >> 5;  // bits of samples >= n are never set
@@ -1509,9 +1511,7 @@ __device__ __forceinline__ void slab_sum(const float* __restrict__ src, const ui
                         }
 #pragma unroll
                         for (int k = 0; k < 8; k++) {
-                            x += v[k].x;
-                            y += v[k].y;
-                            z += v[k].z;
+                            acc.add(v[k]);
                         }
                     }
                 }
@@ -1523,9 +1523,7 @@ __device__ __forceinline__ void slab_sum(const float* __restrict__ src, const ui
                 const int b = __builtin_ctz(m);
                 m &= m - 1;
                 const float3 v = slab_at(src, (size_t)((g << 5) + b), q, npix);
-                x += v.x;
-                y += v.y;
-                z += v.z;
+                acc.add(v);
             }
         }
         return;
@@ -1550,9 +1548,7 @@ __device__ __forceinline__ void slab_sum(const float* __restrict__ src, const ui
 #pragma unroll
                     for (int j = 0; j < kDepth; j++)
                         if ((m >> j) & 1u) {
-                            x += v[j].x;
-                            y += v[j].y;
-                            z += v[j].z;
+                            acc.add(v[j]);
                         }
                 }
             } else {
@@ -1560,9 +1556,7 @@ __device__ __forceinline__ void slab_sum(const float* __restrict__ src, const ui
                     const int j = __builtin_ctz(m);
                     m &= m - 1;
                     const float3 v = slab_at(src, (size_t)(s + j), q, npix);
-                    x += v.x;
-                    y += v.y;
-                    z += v.z;
+                    acc.add(v);
                 }
             }
         }
@@ -1570,30 +1564,43 @@ __device__ __forceinline__ void slab_sum(const float* __restrict__ src, const ui
             const size_t i = (size_t)s * npix + q;
             if ((flags[i >> 5] >> (uint32_t)(i & 31)) & 1u) {
                 const float3 v = slab_at(src, (size_t)s, q, npix);
-                x += v.x;
-                y += v.y;
-                z += v.z;
+                acc.add(v);
             }
         }
         return;
     }
-    for (; s + 4 <= n; s += 4) {  // 4 samples' loads in flight, added in sample order
-        float3 v[4];
+    // a dense slab: kDense samples' loads in flight, added in sample order (kParallel: 8, a part of
+    // few pixels — one rank's rows at 8 GPUs: 131k threads — is latency-bound with fewer)
+    constexpr int kDense = kParallel ? 8 : 4;
+    for (; s + kDense <= n; s += kDense) {
+        float3 v[kDense];
 #pragma unroll
-        for (int j = 0; j < 4; j++) v[j] = slab_at(src, (size_t)(s + j), q, npix);
+        for (int j = 0; j < kDense; j++) v[j] = slab_at(src, (size_t)(s + j), q, npix);
 #pragma unroll
-        for (int j = 0; j < 4; j++) {
-            x += v[j].x;
-            y += v[j].y;
-            z += v[j].z;
+        for (int j = 0; j < kDense; j++) {
+            acc.add(v[j]);
         }
     }
     for (; s < n; s++) {
         const float3 v = slab_at(src, (size_t)s, q, npix);
+        acc.add(v);
+    }
+}
+
+// The image's float32 running sum of a pixel, as slab_walk's accumulator.
+struct SumF32 {
+    float &x, &y, &z;
+    __device__ __forceinline__ void add(const float3 v) {
         x += v.x;
         y += v.y;
         z += v.z;
     }
+};
+template <bool kParallel = false>
+__device__ __forceinline__ void slab_sum(const float* __restrict__ src, const uint32_t* __restrict__ flags, int pm,
+                                         int n, uint32_t q, uint32_t npix, float& x, float& y, float& z) {
+    SumF32 acc{x, y, z};
+    slab_walk<kParallel>(src, flags, pm, n, q, npix, acc);
 }
 
 // One chunk of the fused accumulation: pixels [64 c, 64 c + 64) of the previous batch's

@@ -376,6 +376,7 @@ class Renderer:
         check(lib().pt_ctx_create(device, C.byref(h)))
         self.h = h
         self.num_tris = 0  # triangles of the scene set_scene uploaded (trace_grad's override / gradient rows)
+        self._mom_pixels = 0  # pixels of the part the running moments sum covers (unconverged's mask)
 
     def close(self) -> None:
         if getattr(self, "h", None):
@@ -474,6 +475,88 @@ class Renderer:
         check(lib().pt_ctx_render_progressive(self.h, C.byref(camera.c), C.byref(prm), s_first, s_count,
                                               C.c_void_p(out.data_ptr()), 1, C.byref(st)))
         return out, st.as_dict()
+
+    def _moments_io(self, rows: int, W: int, want, out):
+        """The image and the wanted moments of a part as (img, moments dict, image pointer,
+        pt_moments, is_device): numpy arrays, or with `out` a torch tensor (float32, rows*W*3
+        elements, on this context's device) tensors beside it."""
+        want = tuple(want)
+        for k in want:
+            if k not in _lib.pt_moments.NAMES:
+                raise ValueError(f"want: {k!r} is not one of {_lib.pt_moments.NAMES}")
+        mom, res = _lib.pt_moments(), {}
+        if out is None:
+            img = np.empty((rows, W, 3), dtype=np.float32)
+            for k in want:
+                res[k] = np.empty((rows, W, 3), dtype=np.float32 if k == "sem" else np.float64)
+                setattr(mom, k, res[k].ctypes.data)
+            return img, res, C.c_void_p(img.ctypes.data), mom, 0
+        import torch
+        if not _is_tensor(out) or not out.is_cuda or out.dtype != torch.float32 or out.numel() != rows * W * 3 \
+                or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 tensor with rows*W*3 elements on the context's device")
+        for k in want:
+            res[k] = torch.empty((rows, W, 3), dtype=torch.float32 if k == "sem" else torch.float64, device=out.device)
+            setattr(mom, k, res[k].data_ptr())
+        return out, res, C.c_void_p(out.data_ptr()), mom, 1
+
+    def render_moments(self, camera: Camera, s_first: int, s_count: int, depth: int, seed: int = PT_SEED,
+                       part_index: int = 0, part_count: int = 1, band_rows: int = 1, out=None,
+                       batch_spp: int = 0, samples_per_item: int = 0, want: Sequence[str] = _lib.pt_moments.NAMES):
+        """render_progressive that also keeps the per-pixel sample moments (pt_ctx_render_moments):
+        adds samples [s_first, s_first + s_count) to this context's running moments sum and
+        returns (img, moments, stats). img is the running mean, bit-identical to render() with
+        s_first + s_count samples; moments holds the entries of `want`, each (rows, W, 3):
+        "sum" and "sumsq" (float64: the sums of the float32 samples and of their squares, added
+        in sample order) and "sem" (float32: the standard error of the mean, +inf below two
+        samples). s_first = 0 starts a sum; otherwise it must continue the last moments sum (same
+        camera, depth, seed and partition; a render_progressive sum cannot be continued here, nor
+        the other way round) or PTError is raised. `out`: None (numpy results) or a torch float32
+        tensor on this context's device, written in place; the moments are then tensors there."""
+        W, H = camera.res
+        rows = self.part_rows(H, part_index, part_count, band_rows)
+        prm = _lib.pt_params(s_first + s_count, depth, seed, part_index, part_count, band_rows, batch_spp,
+                             samples_per_item)
+        img, res, img_ptr, mom, dev = self._moments_io(rows, W, want, out)
+        st = _lib.pt_stats()
+        check(lib().pt_ctx_render_moments(self.h, C.byref(camera.c), C.byref(prm), s_first, s_count, img_ptr,
+                                          C.byref(mom), dev, C.byref(st)))
+        self._mom_pixels = rows * W
+        return img, res, st.as_dict()
+
+    def unconverged(self, rel: float, abs: float = 0.0, mask: bool = False):
+        """Pixels of this context's running moments sum that miss the noise target
+        sem <= rel * |mean| + abs in some channel (pt_ctx_unconverged; PTError without a moments
+        sum): the count, or with mask=True (count, uint8 array of the part's pixels, 1 =
+        unconverged). Equal to moments_unconverged() on the same sums."""
+        n = C.c_int64(0)
+        m = np.empty(self._mom_pixels, dtype=np.uint8) if mask else None
+        check(lib().pt_ctx_unconverged(self.h, C.c_float(rel), C.c_float(abs), C.byref(n),
+                                       m.ctypes.data if mask else None, 0))
+        return (n.value, m) if mask else n.value
+
+    def render_converge(self, camera: Camera, depth: int, rel: float, abs: float = 0.0, min_samples: int = 16,
+                        max_samples: int = 4096, step: int = 0, max_unconverged: int = 0, seed: int = PT_SEED,
+                        part_index: int = 0, part_count: int = 1, band_rows: int = 1, out=None, batch_spp: int = 0,
+                        samples_per_item: int = 0, want: Sequence[str] = _lib.pt_moments.NAMES):
+        """Render to a noise target (pt_ctx_render_converge): rounds end at min_samples, then
+        every `step` samples later (step = 0: at twice the samples), never past max_samples; the
+        render stops at the first round end where at most max_unconverged pixels miss
+        sem <= rel * |mean| + abs, or at max_samples. Returns (img, moments, info): img
+        bit-identical to render() with info["spp"] samples, moments as render_moments, info =
+        {"spp", "rounds", "unconverged", "rays", "kernel_ms", "reduce_ms", "total_ms"}. The
+        moments sum stays valid: render_moments can continue it from info["spp"]. A pixel whose
+        samples so far are all zero counts as converged; min_samples is the guard."""
+        W, H = camera.res
+        rows = self.part_rows(H, part_index, part_count, band_rows)
+        prm = _lib.pt_params(0, depth, seed, part_index, part_count, band_rows, batch_spp, samples_per_item)
+        cv = _lib.pt_converge(rel, abs, min_samples, max_samples, step, max_unconverged)
+        img, res, img_ptr, mom, dev = self._moments_io(rows, W, want, out)
+        cs = _lib.pt_converge_stats()
+        check(lib().pt_ctx_render_converge(self.h, C.byref(camera.c), C.byref(prm), C.byref(cv), img_ptr,
+                                           C.byref(mom), dev, C.byref(cs)))
+        self._mom_pixels = rows * W
+        return img, res, cs.as_dict()
 
     def render_rgb8(self, camera: Camera, samples: int, depth: int, gamma: float = 2.2, flip: bool = True,
                     seed: int = PT_SEED, part_index: int = 0, part_count: int = 1, band_rows: int = 1, out=None,
@@ -693,6 +776,25 @@ def render_rgb8(camera: Camera, bvh: BVH, samples: int, depth: int, devices: Seq
                                        C.c_float(gamma), img.ctypes.data, C.byref(st)))
     del cb
     return img, st.as_dict()
+
+
+def moments_unconverged(sum, sumsq, n: int, rel: float, abs: float = 0.0, mask: bool = False):
+    """The convergence count of per-pixel sample moments on the host (pt_moments_unconverged; no
+    device needed): `sum` and `sumsq` (..., 3) float64 as Renderer.render_moments returns them
+    after n samples. A pixel is converged iff n*Q - S*S <= (n-1) * (rel*|S| + abs*n)^2 holds in
+    its three channels (sem <= rel*|mean| + abs without its divisions), evaluated in double; below
+    two samples none is, and a NaN leaves its pixel unconverged. Returns the unconverged count,
+    or with mask=True (count, uint8 array, 1 = unconverged)."""
+    S = np.ascontiguousarray(sum, dtype=np.float64)
+    Q = np.ascontiguousarray(sumsq, dtype=np.float64)
+    if S.shape != Q.shape or S.size % 3:
+        raise ValueError("sum and sumsq must have the same shape, three channels per pixel")
+    npix = S.size // 3
+    cnt = C.c_int64(0)
+    m = np.empty(npix, dtype=np.uint8) if mask else None
+    check(lib().pt_moments_unconverged(S.ctypes.data, Q.ctypes.data, npix, n, C.c_float(rel), C.c_float(abs),
+                                       C.byref(cnt), m.ctypes.data if mask else None))
+    return (cnt.value, m) if mask else cnt.value
 
 
 def devices_release() -> None:

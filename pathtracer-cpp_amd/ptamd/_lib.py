@@ -32,6 +32,7 @@ EXPORTED = (
     "pt_bvh_trace", "pt_ctx_trace", "pt_debug_ctx_plan", "pt_debug_walk_placement",
     "pt_bvh_trace_grad", "pt_ctx_trace_grad",
     "pt_debug_emit_reject", "pt_debug_emit_box", "pt_debug_ctx_emit_reject", "pt_debug_emit_slab_reject",
+    "pt_ctx_render_moments", "pt_moments_unconverged", "pt_ctx_unconverged", "pt_ctx_render_converge",
 )
 PT_MAX_DEVICES = 16
 
@@ -123,6 +124,25 @@ class pt_grad_stats(C.Structure):
         d = self.trace.as_dict()
         d.update(terms=self.terms, grad_ms=self.grad_ms, lds_table=self.lds_table)
         return d
+
+
+class pt_moments(C.Structure):
+    """Per-pixel sample moments (include/pt_hip.h); a NULL pointer skips the output."""
+    NAMES = ("sum", "sumsq", "sem")
+    _fields_ = [(k, C.c_void_p) for k in NAMES]
+
+
+class pt_converge(C.Structure):
+    _fields_ = [("rel", C.c_float), ("abs", C.c_float), ("min_spp", C.c_int32), ("max_spp", C.c_int32),
+                ("step", C.c_int32), ("max_unconverged", C.c_int64)]
+
+
+class pt_converge_stats(C.Structure):
+    _fields_ = [("spp", C.c_int32), ("rounds", C.c_int32), ("unconverged", C.c_int64), ("rays", C.c_uint64),
+                ("kernel_ms", C.c_double), ("reduce_ms", C.c_double), ("total_ms", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class pt_aov(C.Structure):
@@ -230,6 +250,14 @@ def lib() -> C.CDLL:
                                             C.POINTER(pt_trace_grad_io), C.POINTER(pt_grad_stats)]
             L.pt_ctx_trace_grad.argtypes = [P, P, P, C.c_int64, C.POINTER(pt_trace_params), C.POINTER(pt_trace_grad_io),
                                             C.c_int, C.POINTER(pt_grad_stats)]
+        if hasattr(L, "pt_ctx_render_moments"):  # absent from older builds used in A/B runs
+            L.pt_ctx_render_moments.argtypes = [P, C.POINTER(pt_camera), C.POINTER(pt_params), C.c_int32, C.c_int32, P,
+                                                C.POINTER(pt_moments), C.c_int, C.POINTER(pt_stats)]
+            L.pt_moments_unconverged.argtypes = [P, P, C.c_int64, C.c_int32, C.c_float, C.c_float,
+                                                 C.POINTER(C.c_int64), P]
+            L.pt_ctx_unconverged.argtypes = [P, C.c_float, C.c_float, C.POINTER(C.c_int64), P, C.c_int]
+            L.pt_ctx_render_converge.argtypes = [P, C.POINTER(pt_camera), C.POINTER(pt_params), C.POINTER(pt_converge), P,
+                                                 C.POINTER(pt_moments), C.c_int, C.POINTER(pt_converge_stats)]
         if hasattr(L, "pt_debug_rccl_failover"):  # test hooks (absent from older builds used in A/B runs)
             L.pt_debug_rccl_failover.argtypes = [C.c_int32, C.c_int32, P]
         if hasattr(L, "pt_debug_rtc_cache"):
