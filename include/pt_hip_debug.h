@@ -106,6 +106,13 @@ int pt_debug_emit_box(const pt_scene* scene, float out[6]);
  * render kernels are, the hipRTC scene kernel under PT_RTC_DEFINES=PT_COUNT_EARLY=1 (else 0).
  * Any pointer may be NULL. */
 int pt_debug_ctx_emit_reject(const pt_ctx* ctx, int32_t* on, float box[6], uint64_t* early);
+/* Test hook, no device needed: the loop control of the flat kernels' shared camera-ray stock
+ * (pt_raystack.h), one decision per call. which = 0: 1 if the generator runs with `count` rays in
+ * stock, n lanes without a path, `reserve`, and flag = the pool is dry; 1: count after a fill in
+ * which n lanes got an item; 2: 1 if that fill found the pool dry; 3: the slot the lane of rank n
+ * takes (< 0: none); 4: count after n lanes asked; 5: 1 if the wave is done (flag = a lane is on a
+ * path, n = the pool is dry). < 0 on a bad `which`. */
+int pt_debug_ray_stack(int32_t which, int32_t count, int32_t n, int32_t reserve, int32_t flag);
 /* Test hook: process-wide counters. which = 0: contexts created (pt_ctx_create), 1: scene
  * uploads (pt_ctx_set_scene), 2: cached multi-device context sets live, 3: uploads skipped
  * because a cached context already held the same scene. */

@@ -53,13 +53,16 @@ static_assert(kNodeU4<8, kWideF16> == kWideNodeU4(8, kWideF16) && kNodeU4<4, kWi
 // kPF: the wide tree's child planes (kWideByte, kWideF16 binary16 integers, kWideF32 floats).
 // Float planes (kWideF32, PT_WIDE_PLANES=f32) are register-allocated for 5 waves: at 6 they
 // spill 18 VGPRs and run at half speed (config 4: 10.3 against 18.4 Grays/s, profiles/r06_planes).
-template <bool kLdsScene, bool kFlat, int kWide = 0, int kPF = kWideByte>
+// kStack = false: the flat kernel's PerLaneRays form (test hook PT_RAY_STACK=0).
+template <bool kLdsScene, bool kFlat, int kWide = 0, int kPF = kWideByte, bool kStack = true>
 __global__ __launch_bounds__(kBlock, kPF == kWideF32 ? 5 : kWide == 8 ? PT_WIDE8_WAVES : kWide == 4 ? PT_WIDE4_WAVES : PT_WAVES)
 void pt_trace_kernel(TraceArgs A) {
     if constexpr (kWide > 0)
         trace_body_wide<kWide, kPF, kLdsScene>(A);
-    else if constexpr (kFlat)
+    else if constexpr (kFlat && kStack)
         trace_body_flat<TableBoxMask>(A);
+    else if constexpr (kFlat)
+        trace_body_flat<PerLaneRays<TableBoxMask>>(A);
     else
         trace_body<kLdsScene>(A);
 }
@@ -792,7 +795,9 @@ int plan_render(pt_ctx* c, const PartShape& shape, const pt_params* prm, int s_l
     const bool rtc_switch = !hook_off("PT_RTC_SWITCH");
     P.rtc_switch_at = hook_int("PT_RTC_SWITCH_AT", -1);
     if (P.flat && c->rtc_job.valid()) rtc_resolve(c, !rtc_switch && (double)shape.npix * (spp - s_lo) >= kRtcWaitPaths);
-    P.kern = P.flat        ? (c->flat_fast ? (TraceKernel)c->flat_fast : pt_trace_kernel<true, true>)
+    P.kern = P.flat        ? (c->flat_fast                    ? (TraceKernel)c->flat_fast
+                              : ray_stack_on(c->has_specular) ? pt_trace_kernel<true, true>
+                                                              : pt_trace_kernel<true, true, 0, kWideByte, false>)
              : P.wide      ? wide_kernel(c->meta.wide_width, c->meta.wide_fmt, P.lds_scene)
              : P.lds_scene ? pt_trace_kernel<true, false>
                            : pt_trace_kernel<false, false>;
@@ -926,6 +931,7 @@ int fill_trace_args(pt_ctx* c, const RenderPlan& P, const pt_camera* cam, const 
     // camera rays generated once this many lanes want one: 32, 40 in scenes with a
     // SPECULAR material (config 3: +0.6 %, Cornell flat at 32-40; profiles/r04_knobs)
     A.regen_thresh = std::max(1, std::min(64, hook_int("PT_REGEN_THRESH", c->has_specular ? 40 : 32)));
+    A.ray_reserve = ray_reserve();
     A.flags_pm = P.flags_pm;
     A.acc_chunks = 0;
     return PT_OK;
@@ -1086,6 +1092,9 @@ void report_stamps(const pt_ctx* c, bool wide, const unsigned long long* h_ctr) 
             fprintf(stderr, "[stamps] per flat wave-iteration: pairs %.1f, pair rounds %.2f, max pairs of a lane %.2f, "
                     "rays credited %.2f (%llu wave-iterations)\n",
                 hs[8] / it, hs[9] / it, hs[10] / it, (double)h_ctr[1] / it, hs[7]);
+        if (!wide)
+            fprintf(stderr, "[stamps] camera-ray generator: %.4f runs per wave-iteration, %.2f lanes per run (%llu runs)\n",
+                    hs[11] / it, (double)hs[12] / (double)(hs[11] ? hs[11] : 1), hs[11]);
     }
 }
 #endif
@@ -2285,6 +2294,19 @@ int pt_debug_emit_slab_reject(const float* box6, const float* org, const float* 
         out[i] = emit_slab_reject(v3{b[0], b[1], b[2]}, v3{b[3], b[4], b[5]}, v3{o[0], o[1], o[2]}, v3{v[0], v[1], v[2]}) ? 1 : 0;
     }
     return PT_OK;
+}
+
+// Test hook (no device needed): the loop control of the shared camera-ray stock (pt_raystack.h).
+int pt_debug_ray_stack(int32_t which, int32_t count, int32_t n, int32_t reserve, int32_t flag) {
+    switch (which) {
+        case 0: return ray_stack_generate(count, n, reserve, flag != 0) ? 1 : 0;
+        case 1: return ray_stack_filled(count, n);
+        case 2: return ray_stack_dry(count, n) ? 1 : 0;
+        case 3: return ray_stack_slot(count, n);
+        case 4: return ray_stack_taken(count, n);
+        case 5: return ray_stack_done(flag != 0, count, n != 0) ? 1 : 0;
+    }
+    return set_error(PT_E_ARG, "pt_debug_ray_stack: which = %d", which);
 }
 
 // Test hook: the launch plan of the context's last render (pt_hip_debug.h).

@@ -27,6 +27,19 @@ inline int hook_int(const char* name, int dflt) {
     const char* e = hook_env(name);
     return (e && *e) ? atoi(e) : dflt;
 }
+// Whether the flat kernels share the wave's stock of prefetched camera rays among its lanes
+//  or keep each ray to the lane that generated it: shared in scenes without a
+// SPECULAR material (headline +1.1 %, 4096^2 depth 8 +1.9 %), per lane in scenes with one (modified
+// Cornell r = 0.3: -0.7 % shared; profiles/ray_stack). PT_RAY_STACK=0 / 1 (test hook, A/B) forces
+// either. Read when a scene is set (the scene kernel's source) and when a render is planned.
+inline bool ray_stack_on(bool specular) { return hook_int("PT_RAY_STACK", specular ? 0 : 1) != 0; }
+// PT_RAY_RESERVE (tuning hook): the shared stock refills once it holds fewer rays than the lanes
+// without a path plus this; 0..64, 0 measured best (profiles/ray_stack). A constant of the scene
+// kernel's source, TraceArgs::ray_reserve for the offline kernels.
+inline int ray_reserve() {
+    const int r = hook_int("PT_RAY_RESERVE", 0);
+    return r < 0 ? 0 : r > 64 ? 64 : r;
+}
 // Byte counts: any base strtoull takes (0x..., 0...).
 inline size_t hook_size(const char* name, size_t dflt) {
     const char* e = hook_env(name);

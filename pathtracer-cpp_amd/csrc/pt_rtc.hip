@@ -42,9 +42,10 @@ extern char** environ;
 #include "pt_sha256.h"
 #include "pt_trace.h"
 
-// Sources of pt_trace.h, pt_math.h and pt_hip.h, embedded at build time (build/pt_rtc_blob.cpp).
+// Sources of pt_trace.h, pt_math.h, pt_raystack.h and pt_hip.h, embedded at build time (build/pt_rtc_blob.cpp).
 extern "C" const char* pt_rtc_src_trace;
 extern "C" const char* pt_rtc_src_math;
+extern "C" const char* pt_rtc_src_stack;
 extern "C" const char* pt_rtc_src_hip;
 
 namespace pt {
@@ -298,6 +299,7 @@ std::string flat_mask_source(const std::vector<f4>& leaves, int n, bool specular
            (sign ? "1" : "0") + ")\n" + "#define KBOX " + (nbox > 0 ? "(!KSIGN)" : "0") + "\n" +
            "namespace pt {\nstruct SceneBoxMask {\n    static constexpr bool kSignMask = KSIGN;\n"
            "    static constexpr bool kBoxPairs = KBOX;\n    static constexpr bool kCamInvGen = PT_CAM_INV == 2;\n"
+           "    static constexpr bool kRayStack = PT_RAY_STACK != 0;\n"
            "    static constexpr int kBoxes = " + std::to_string(nbox) +
            ";\n    static constexpr uint16_t kBoxTab[" + std::to_string(std::max<size_t>(1, box_tab.size())) + "] = " + tabs +
            ";\n    static constexpr bool kMask32 = " +
@@ -371,6 +373,7 @@ std::string rtc_flat_source(const std::vector<f4>& leaves, int n, bool specular,
     // without it the kernel has VGPRs to spare at 8 waves and plain threadIdx.x is +0.5-1.2 %
     // (configs 2, 5); with it plain threadIdx.x costs SGPR spill lanes, -0.3 % (config 3)
     return fl + "\n" + rtc_defines() + (emit.on && emit.sign_only ? "#define PT_EMIT_SIGN_ONLY 1\n" : "") +
+           (ray_stack_on(specular) ? "#define PT_RAY_RESERVE " + std::to_string(ray_reserve()) + "\n" : "#define PT_RAY_STACK 0\n") +
            "#define PT_WAVES " + std::to_string(rtc_waves()) +
            "\n#define PT_FLAT_ONLY 1\n#ifndef PT_CAM_KERNARG\n#define PT_CAM_KERNARG 0\n#endif\n"
            "#ifndef PT_FRESH_TID\n#define PT_FRESH_TID " + (specular ? "1" : "0") + "\n#endif\n"
@@ -465,7 +468,7 @@ std::string rtc_key(const std::string& src) {
     Sha256 k;
     k.update("pathtracer-amd hipRTC code object v1");
     k.update(src.c_str(), src.size() + 1);
-    for (const char* h : {pt_rtc_src_trace, pt_rtc_src_math, pt_rtc_src_hip}) k.update(h, strlen(h) + 1);
+    for (const char* h : {pt_rtc_src_trace, pt_rtc_src_math, pt_rtc_src_stack, pt_rtc_src_hip}) k.update(h, strlen(h) + 1);
     for (const std::string& f : rtc_flags()) k.update(f.c_str(), f.size() + 1);
     int maj = 0, mnr = 0;
     (void)hiprtcVersion(&maj, &mnr);
@@ -697,12 +700,12 @@ bool rtc_server_compile(const std::string& src, RtcCode& out) {
         const uint64_t len = n;
         return put(&len, 8) && put(str, n);
     };
-    const char* hdrs[] = {pt_rtc_src_trace, pt_rtc_src_math, pt_rtc_src_hip};
-    const char* names[] = {"pt_trace.h", "pt_math.h", "pt_hip.h"};
+    const char* hdrs[] = {pt_rtc_src_trace, pt_rtc_src_math, pt_rtc_src_stack, pt_rtc_src_hip};
+    const char* names[] = {"pt_trace.h", "pt_math.h", "pt_raystack.h", "pt_hip.h"};
     const std::vector<std::string> flags = rtc_flags();
-    const uint32_t head[3] = {0x51525450u /* "PTRQ" */, 3u, (uint32_t)flags.size()};
+    const uint32_t head[3] = {0x51525450u /* "PTRQ" */, 4u, (uint32_t)flags.size()};
     bool ok = put(head, 12) && put_str(src.data(), src.size());
-    for (int i = 0; ok && i < 3; i++) ok = put_str(names[i], strlen(names[i])) && put_str(hdrs[i], strlen(hdrs[i]));
+    for (int i = 0; ok && i < 4; i++) ok = put_str(names[i], strlen(names[i])) && put_str(hdrs[i], strlen(hdrs[i]));
     for (size_t i = 0; ok && i < flags.size(); i++) ok = put_str(flags[i].data(), flags[i].size());
     uint32_t resp[2] = {0, 0};
     uint64_t n = 0;
@@ -740,10 +743,10 @@ std::shared_ptr<const RtcCode> rtc_compile(const std::string& src, const std::st
         if (!out->code.empty()) rtc_disk_store(key, out->code);
         return out;
     }
-    const char* hdrs[] = {pt_rtc_src_trace, pt_rtc_src_math, pt_rtc_src_hip};
-    const char* names[] = {"pt_trace.h", "pt_math.h", "pt_hip.h"};
+    const char* hdrs[] = {pt_rtc_src_trace, pt_rtc_src_math, pt_rtc_src_stack, pt_rtc_src_hip};
+    const char* names[] = {"pt_trace.h", "pt_math.h", "pt_raystack.h", "pt_hip.h"};
     hiprtcProgram prog;
-    if (hiprtcCreateProgram(&prog, src.c_str(), "pt_trace_flat_rtc.hip", 3, hdrs, names) != HIPRTC_SUCCESS) {
+    if (hiprtcCreateProgram(&prog, src.c_str(), "pt_trace_flat_rtc.hip", 4, hdrs, names) != HIPRTC_SUCCESS) {
         out->status = "hiprtcCreateProgram failed";
         return out;
     }

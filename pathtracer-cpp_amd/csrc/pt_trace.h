@@ -20,11 +20,13 @@
 
 #include "pt_hip.h"
 #include "pt_math.h"
+#include "pt_raystack.h"
 
 namespace pt {
 
 constexpr int kBlock = 256;
 constexpr int kWave = 64;
+static_assert(kRaySlots == kWave, "one prefetched camera ray per lane (pt_raystack.h)");
 constexpr int kMaxSpecularIters = 1 << 16;  // bound for material.h:20-23 (reference: unbounded)
 #ifndef PT_CHUNK  // >= kWave (64)
 #define PT_CHUNK 1024  // Cornell headline: 64 -> 18.6, 128 -> 36.8, 256 -> 42.8, 1024 -> 43.1, 4096 -> 42.6 Grays/s
@@ -59,6 +61,7 @@ constexpr int kMaxFlatLeaves = 64;
 #endif
 constexpr int kStampSections = 23;  // start, box mask, pair phase, shade, fold, intersect, waves,
                                     // pair iterations, pairs, pair rounds, max pairs of a lane;
+                                    // flat: 11 camera-ray generator runs, 12 lanes generating;
                                     // wide: 10 outer iterations, 11 shading lanes, 12 new paths,
                                     // 13 drain rounds, 14 drained entries, 15 end-of-iteration
                                     // drain rounds, 16 path ends; wide launch timeline (100 MHz
@@ -283,7 +286,8 @@ struct TraceArgs {
     uint32_t* __restrict__ flags;
     int flags_pm;
     const uint32_t* __restrict__ acc_flags;  // the previous batch's flags (fused accumulation)
-    FlatLeaves flat;                     // kFlat kernels with the generic box loop
+    int ray_reserve;                     // kFlat, shared stock: generate once count < lanes without a path + this
+    FlatLeaves flat;                    // kFlat kernels with the generic box loop
 };
 
 // compact row r of this part -> image row h (row h belongs to part (h / band) % parts)
@@ -435,6 +439,7 @@ struct TableBoxMask {
     static constexpr bool kDarkKnown = false;  // kDark is not known at compile time: finish_path reads A.dark
     static constexpr bool kBoxPairs = false;   // mask bits are leaves (hipRTC kernels may use box-level pairs)
     static constexpr bool kCamInvGen = false;  // a camera ray's carried inv: start branch (60 VGPRs; generator: 64)
+    static constexpr bool kRayStack = true;    // prefetched camera rays shared by the wave's lanes (§3.18)
     static constexpr int kBoxes = 0;
     static constexpr uint16_t kBoxTab[1] = {0};
     static constexpr bool kDark = false;
@@ -472,6 +477,16 @@ struct FastTableMask : TableBoxMask {
     // the form that leaves each kernel without a scratch reservation at its 64 VGPRs (with the
     // specular sampler the generator form, 61 VGPRs; without it the start branch, 60)
     static constexpr bool kCamInvGen = kSpec;
+    // the per-lane camera rays: with the shared stock (§3.18) each of the four kernels reserves
+    // 20 B of scratch at its 64 VGPRs (per-lane: none); they run cold first frames only
+    static constexpr bool kRayStack = false;
+};
+
+// A box mask whose kernel keeps each lane's prefetched camera ray to that lane, as before §3.18
+// (test hook PT_RAY_STACK=0: the A/B against the shared stock).
+template <typename Mask>
+struct PerLaneRays : Mask {
+    static constexpr bool kRayStack = false;
 };
 
 // Triangle phase of the flat path for one lane: the triangles of the leaves in `mask`,
@@ -2061,6 +2076,19 @@ __device__ __forceinline__ void count_early_wave(const TraceArgs& A, int lane, u
 #ifndef PT_CAM_INV
 #define PT_CAM_INV 2
 #endif
+// Who may consume a prefetched camera ray (BoxMask::kRayStack): any lane of the
+// wave, from a stock kept as a stack, or only the lane that generated it (0: the form before
+// §3.18: scenes with a SPECULAR material, and the test hook PT_RAY_STACK=0; the host defines it
+// for the hipRTC scene kernel and picks the PerLaneRays instantiation of the generic table kernel).
+#ifndef PT_RAY_STACK
+#define PT_RAY_STACK 1
+#endif
+// The stock's reserve (pt_raystack.h): a constant >= 0 in the hipRTC scene kernel, whose source
+// defines it (TraceArgs::ray_reserve read in the loop was a scalar load and a wait at the top of
+// every iteration); the offline kernels read the kernel argument.
+#ifndef PT_RAY_RESERVE
+#define PT_RAY_RESERVE (-1)
+#endif
 __device__ __forceinline__ int fresh_tid() {
     int t = (int)threadIdx.x;
     if (PT_FRESH_TID) asm volatile("" : "+v"(t));
@@ -2111,6 +2139,10 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
     bool alive = true;      // the lane's generator may still produce paths
     bool active = false;    // lane has a path in flight (slab offset `at`)
     bool has_next = false;  // lane's next camera ray waits in next_ray / next_at (LDS)
+    // BoxMask::kRayStack replaces the two above by wave-uniform state: slots [0, count) of the
+    // wave's stock hold a camera ray, and `dry` once the work pool has no item left
+    int count = 0;
+    bool dry = false;
     uint32_t at = 0;
     Lcg g{0};
     v3 o{0, 0, 0}, d{0, 0, 0};
@@ -2131,51 +2163,114 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
 
     while (true) {
         PT_STAMP(st_a)
-        // Camera rays are generated one path ahead, and only once at least
-        // A.regen_thresh lanes of the wave want one (or nothing else is left to do):
-        // the generator then runs with many lanes active instead of the few whose path
-        // just ended. A lane idles only when its path ends before its slot is refilled.
+        // Camera rays are generated ahead of the paths that will use them, in batches, so the
+        // generator runs with many lanes active instead of the few whose path just ended.
         // The prefetched ray lives in LDS, not in registers (fewer VGPRs -> more waves).
-        const bool want = alive && !has_next;
-        const int n_want = (int)__popcll(__ballot(want));
-        if (n_want > 0 && (n_want >= A.regen_thresh || !__any(active || has_next))) {
-            uint32_t item = 0;
-            claim_item(A, lane, want, pool, alive, item);
-            if (want && alive) {
-                const uint32_t blk = fdiv(item, A.div_npix);  // item = blk * npix + q, sample s_begin + blk
-                Lcg gn{0};
-                v3 on, nd;
-                camera_ray(A, (int)(item - blk * (uint32_t)A.npix), A.s_begin + (int)blk, gn, on, nd);
+        // The generator proper, for a lane that claimed `item`: its camera ray into the lane's own
+        // LDS row (and next_inv).
+        auto generate = [&](uint32_t item) {
+            const uint32_t blk = fdiv(item, A.div_npix);  // item = blk * npix + q, sample s_begin + blk
+            Lcg gn{0};
+            v3 on, nd;
+            camera_ray(A, (int)(item - blk * (uint32_t)A.npix), A.s_begin + (int)blk, gn, on, nd);
 #ifdef PT_EXP_DUP_CAMF  // measurement only: the camera ray once more
-                {
-                    uint32_t it2 = item;
-                    asm volatile("" : "+v"(it2));
-                    Lcg g2{0};
-                    v3 o2, d2;
-                    camera_ray(A, (int)(it2 - blk * (uint32_t)A.npix), A.s_begin + (int)blk, g2, o2, d2);
-                    asm volatile("" ::"v"(d2.x), "v"(d2.y), "v"(d2.z), "v"(g2.s));
-                }
-#endif
-                next_ray[fresh_tid()] = make_float4(nd.x, nd.y, nd.z, __uint_as_float(gn.s));
-                next_at[fresh_tid()] = item;
-                if constexpr (kGenInv) next_inv = v3{rcp_exact(nd.x), rcp_exact(nd.y), rcp_exact(nd.z)};
-                has_next = true;
+            {
+                uint32_t it2 = item;
+                asm volatile("" : "+v"(it2));
+                Lcg g2{0};
+                v3 o2, d2;
+                camera_ray(A, (int)(it2 - blk * (uint32_t)A.npix), A.s_begin + (int)blk, g2, o2, d2);
+                asm volatile("" ::"v"(d2.x), "v"(d2.y), "v"(d2.z), "v"(g2.s));
             }
+#endif
+            next_ray[fresh_tid()] = make_float4(nd.x, nd.y, nd.z, __uint_as_float(gn.s));
+            next_at[fresh_tid()] = item;
+            if constexpr (kGenInv) next_inv = v3{rcp_exact(nd.x), rcp_exact(nd.y), rcp_exact(nd.z)};
+        };
+        if constexpr (BoxMask::kRayStack) {
+            // The shared stock (pt_raystack.h): slots [0, count) hold rays, slot s
+            // being LDS row s of the wave and lane s's next_inv, and any lane takes any slot: a
+            // sample's radiance goes to its own slab offset, so which lane traces it is free. The
+            // generator runs only when the stock cannot serve the lanes without a path, and then
+            // lanes count..63 refill every empty slot at once.
+            const unsigned long long need = __ballot(!active);
+            const int n_need = (int)__popcll(need);
+            if (ray_stack_generate(count, n_need, PT_RAY_RESERVE >= 0 ? PT_RAY_RESERVE : A.ray_reserve, dry)) {
+                const bool want = lane >= count;
+                bool got = true;
+                uint32_t item = 0;
+                claim_item(A, lane, want, pool, got, item);  // ranks in lane order: the lanes that get one are a prefix
+                if (want && got) generate(item);
+                const int n_got = (int)__popcll(__ballot(want && got));
+#ifdef PT_STAMPS
+                stamp_acc[11] += 1;
+                stamp_acc[12] += (uint32_t)n_got;
+#endif
+                dry = ray_stack_dry(count, n_got);
+                count = ray_stack_filled(count, n_got);
+                wave_lds_sync();  // rows written here are read by other lanes below
+            }
+            if (n_need > 0 && count > 0) {  // wave-uniform: all 64 lanes take part in the bpermutes
+                const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32),
+                                                                __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
+                const int slot = ray_stack_slot(count, rank);
+                const bool take = !active && slot >= 0;
+                // the owning lane's next_inv, fetched by all 64 lanes (a disabled source lane would yield
+                // 0) and kept by the takers: ds_bpermute reads lane (address / 4) mod 64, so a lane that
+                // takes nothing (any slot value) fetches some lane's and drops it
+                v3 ti{0, 0, 0};
+                if constexpr (kGenInv)
+                    ti = v3{lane_float(slot << 2, next_inv.x), lane_float(slot << 2, next_inv.y),
+                            lane_float(slot << 2, next_inv.z)};
+                if (take) {
+                    const int t0 = (fresh_tid() & ~(kWave - 1)) + slot;  // slot in [0, count): a row of this wave
+                    const float4 nr = next_ray[t0];
+                    at = next_at[t0];
+                    g.s = __float_as_uint(nr.w);
+                    d = v3{nr.x, nr.y, nr.z};
+                    if constexpr (kGenInv) inv = ti;
+                    else if constexpr (kCarry) inv = v3{rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z)};  // bvh.h:157
+                    o = v3{A.pos_x, A.pos_y, A.pos_z};
+                    k = 0;
+                    active = true;
+                }
+                count = ray_stack_taken(count, n_need);
+            }
+            if (ray_stack_done(__any(active), count, dry)) break;
+        } else {
+            // The per-lane form (PT_RAY_STACK=0): a lane consumes only the ray in its own row, one
+            // path ahead, and the generator runs once at least A.regen_thresh lanes of the wave
+            // want one (or nothing else is left to do). A lane idles when its path ends before its
+            // slot is refilled.
+            const bool want = alive && !has_next;
+            const int n_want = (int)__popcll(__ballot(want));
+            if (n_want > 0 && (n_want >= A.regen_thresh || !__any(active || has_next))) {
+                uint32_t item = 0;
+                claim_item(A, lane, want, pool, alive, item);
+                if (want && alive) {
+                    generate(item);
+                    has_next = true;
+                }
+#ifdef PT_STAMPS
+                stamp_acc[11] += 1;
+                stamp_acc[12] += (uint32_t)__popcll(__ballot(want && alive));
+#endif
+            }
+            if (!active && has_next) {
+                const int t0 = fresh_tid();
+                const float4 nr = next_ray[t0];
+                at = next_at[t0];
+                g.s = __float_as_uint(nr.w);
+                d = v3{nr.x, nr.y, nr.z};
+                if constexpr (kGenInv) inv = next_inv;
+                else if constexpr (kCarry) inv = v3{rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z)};  // bvh.h:157
+                o = v3{A.pos_x, A.pos_y, A.pos_z};
+                k = 0;
+                active = true;
+                has_next = false;
+            }
+            if (!__any(active)) break;
         }
-        if (!active && has_next) {
-            const int t0 = fresh_tid();
-            const float4 nr = next_ray[t0];
-            at = next_at[t0];
-            g.s = __float_as_uint(nr.w);
-            d = v3{nr.x, nr.y, nr.z};
-            if constexpr (kGenInv) inv = next_inv;
-            else if constexpr (kCarry) inv = v3{rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z)};  // bvh.h:157
-            o = v3{A.pos_x, A.pos_y, A.pos_z};
-            k = 0;
-            active = true;
-            has_next = false;
-        }
-        if (!__any(active)) break;
         PT_STAMP(st_b)
 
         // ---- BVH::intersect (bvh.h:156-183); trace(depth == 0) returns 0 without

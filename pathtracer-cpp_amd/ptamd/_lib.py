@@ -31,7 +31,7 @@ EXPORTED = (
     "pt_bvh_intersect", "pt_ctx_intersect", "pt_ctx_render_aov",
     "pt_bvh_trace", "pt_ctx_trace", "pt_debug_ctx_plan", "pt_debug_walk_placement",
     "pt_bvh_trace_grad", "pt_ctx_trace_grad",
-    "pt_debug_emit_reject", "pt_debug_emit_box", "pt_debug_ctx_emit_reject", "pt_debug_emit_slab_reject",
+    "pt_debug_emit_reject", "pt_debug_emit_box", "pt_debug_ctx_emit_reject", "pt_debug_emit_slab_reject", "pt_debug_ray_stack",
     "pt_ctx_render_moments", "pt_moments_unconverged", "pt_ctx_unconverged", "pt_ctx_render_converge",
 )
 PT_MAX_DEVICES = 16

@@ -20,6 +20,11 @@ wave-iteration the lanes trace one segment each of paths at mixed depths. Two qu
    itself fails the reference's slab test), and for comparison the last rays that do hit an
    emitter. Share of last rays and of rejected ones among all rays, rays credited per
    wave-iteration, (lane, leaf) pairs and pair rounds per iteration, without a rule and with each.
+4. Camera-ray generator: the traced iterations of these paths under the slab
+   rule, replayed through the loop control alone, for the per-lane prefetch (a lane consumes only
+   the ray in its own slot; the generator runs once `thresh` lanes want one) and the shared stock
+   (any lane takes any slot; the generator runs when the stock cannot serve the lanes without a
+   path, and refills every empty slot). Generator runs per iteration, lanes per run, lanes tracing.
 
 usage: python scripts/wave_sim.py [--scene cornell|mcornell] [--rough R] [--paths N] [--depth D]
 """
@@ -251,6 +256,54 @@ def simulate(segs, trips, lanes=64):
     return its
 
 
+def generator_policies(lengths, lanes=64, threshes=(32, 40, 48), reserves=(0, 8)):
+    """Question 4. `lengths`: traced iterations per path (>= 1), in work-item order. Steady state
+    only: a run stops when the paths run out."""
+    def figures(runs, gen, tracing, iters):
+        return {"generator_runs_per_iteration": runs / iters, "lanes_per_run": gen / max(runs, 1),
+                "lanes_tracing": tracing / iters, "iterations": iters}
+
+    def per_lane(thresh):
+        rem, nxt, i = np.zeros(lanes, int), np.zeros(lanes, int), 0  # nxt: the prefetched path's length (0: none)
+        runs = gen = tracing = iters = 0
+        while True:
+            want = nxt == 0
+            if want.sum() >= thresh or (not (rem > 0).any() and not (nxt > 0).any()):
+                n = int(want.sum())
+                if i + n > len(lengths):
+                    break
+                nxt[want] = lengths[i:i + n]
+                i, runs, gen = i + n, runs + 1, gen + n
+            take = (rem == 0) & (nxt > 0)
+            rem[take], nxt[take] = nxt[take], 0
+            act = rem > 0
+            tracing, iters = tracing + int(act.sum()), iters + 1
+            rem[act] -= 1
+        return figures(runs, gen, tracing, iters)
+
+    def stack(reserve):
+        rem, stock, i = np.zeros(lanes, int), [], 0
+        runs = gen = tracing = iters = 0
+        while True:
+            need = np.flatnonzero(rem == 0)
+            if len(stock) < lanes and len(stock) < len(need) + reserve:
+                n = lanes - len(stock)
+                if i + n > len(lengths):
+                    break
+                stock += list(lengths[i:i + n])
+                i, runs, gen = i + n, runs + 1, gen + n
+            for lane in need[:len(stock)]:
+                rem[lane] = stock.pop()
+            act = rem > 0
+            tracing, iters = tracing + int(act.sum()), iters + 1
+            rem[act] -= 1
+        return figures(runs, gen, tracing, iters)
+
+    out = {f"per_lane_thresh_{t}": per_lane(t) for t in threshes}
+    out.update({f"shared_stock_reserve_{r}": stack(r) for r in reserves})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scene", choices=["cornell", "mcornell"], default="cornell")
@@ -308,6 +361,11 @@ def main():
         "with": with_rule(rej),
         "with_slab": with_rule(slab),
     }
+    # 4. the camera-ray generator's cadence under both policies (the slab rule's path lengths)
+    lengths = np.array([max(1, len(sg) - (1 if x else 0)) for sg, x in zip(segs, slab)])
+    out["camera_ray_generator"] = {"traced_iterations_per_path": float(lengths.mean()),
+                                   "length_histogram": np.bincount(lengths, minlength=a.depth + 1).tolist(),
+                                   **generator_policies(lengths)}
     print(json.dumps(out, indent=1))
 
 
