@@ -16,6 +16,7 @@
  *                                       triangle.h:45-49 (the first hit of a sample, per pixel)
  *   pt_ctx_render_moments / pt_ctx_unconverged / pt_ctx_render_converge: the render's per-pixel
  *                                       sample moments, their error estimate, rendering to a noise target
+ *   pt_ctx_render_adaptive: the same with the later rounds only for the pixels that miss the target
  *   pt_bvh_build                     <- BVH::build()  bvh.h:79-155 (find_best_axis 48-78)
  *   pt_camera_init                   <- Camera::Camera() camera.h:33-61
  *   pt_sample_seed                   <- rng.h:32 global LCG (stream policy, see below)
@@ -329,6 +330,52 @@ typedef struct pt_converge_stats {
  * pt_ctx_render (the rounds still run and the results are written). */
 int pt_ctx_render_converge(pt_ctx* ctx, const pt_camera* cam, const pt_params* params, const pt_converge* conv,
                            float* out, const pt_moments* mom, int out_is_device, pt_converge_stats* cs);
+
+/* Adaptive sampling: pt_ctx_render_converge that spends its later rounds only on the pixels that
+ * still miss the criterion. The round boundaries are pt_ctx_render_converge's. Dense rounds give
+ * every pixel of the part the round's samples (the render kernels, as pt_ctx_render_moments). At
+ * the first boundary whose unconverged count is <= sparse_below * npix (and > max_unconverged) the
+ * render switches to per-pixel rounds and stays there: the pixels unconverged at that boundary
+ * become the active list, every other pixel is frozen with n_p = that boundary. A per-pixel round
+ * gives the listed pixels samples [n_k, n_{k+1}); then the criterion is evaluated over the list
+ * alone with n = n_{k+1}, and the pixels that meet it leave with n_p = n_{k+1}. A frozen pixel is
+ * never evaluated or sampled again, so the active pixels always share one sample count and the
+ * list only shrinks. The render stops when the list holds at most max_unconverged pixels, or at
+ * max_spp; the pixels still listed keep the last boundary as n_p.
+ *
+ * Per pixel and channel, with the pixel's own n_p: out = (the float32 in-order sum of samples
+ * 0..n_p-1) / (float)n_p, bit-identical to pt_ctx_render at spp = n_p; mom->sum and mom->sumsq are
+ * the sums above over those n_p samples; mom->sem uses n = n_p; spp_out[q] = n_p. Nothing depends
+ * on the order of the list or on how a round is cut into launches. A per-pixel round runs the
+ * binary walk (pt_ctx_trace's kernel fed with the render's camera rays), which on small scenes is
+ * slower per ray than the render kernels: sparse_below is the active fraction below which it pays. */
+typedef struct pt_adaptive {
+    pt_converge conv;            /* criterion, min_spp, max_spp, step, max_unconverged: as pt_ctx_render_converge */
+    float sparse_below;          /* 0: the library's default for the scene's kernel family (flat, wide, tree);
+                                    < 0: never switch (the call is then pt_ctx_render_converge);
+                                    >= 1: per-pixel rounds from the first boundary on */
+} pt_adaptive;
+typedef struct pt_adaptive_stats {
+    int32_t rounds;              /* boundaries evaluated */
+    int32_t dense_rounds;        /* of them, rounds rendered for every pixel */
+    int32_t max_spp;             /* the largest n_p (the last boundary) */
+    int32_t sparse_launches;     /* trace launches of the per-pixel rounds */
+    int64_t unconverged;         /* pixels that miss the criterion at the end (the final list, or count) */
+    int64_t samples;             /* sum of n_p over the part: the pixel-samples rendered */
+    uint64_t rays;               /* all rounds */
+    uint64_t sparse_rays;        /* of them, rays of the per-pixel rounds */
+    double kernel_ms, reduce_ms, total_ms;   /* reduce_ms: accumulation, criterion and list passes */
+    double sparse_kernel_ms;     /* of kernel_ms, the trace kernels of the per-pixel rounds */
+} pt_adaptive_stats;
+/* params->spp is ignored. out, mom, spp_out (npix int32) and st are optional; out_is_device covers
+ * out, the pointers of mom and spp_out. If a per-pixel round ran, the context's running sum is no
+ * longer uniform and ends (pt_ctx_unconverged and a pt_ctx_render_moments continuation then return
+ * PT_E_ARG, as after any other render); otherwise the state is pt_ctx_render_converge's and stays
+ * valid. Argument errors and PT_E_RUNAWAY are reported as by pt_ctx_render_converge. The caveat of
+ * the criterion holds per pixel: one whose first min_spp samples are all +0 is frozen there. */
+int pt_ctx_render_adaptive(pt_ctx* ctx, const pt_camera* cam, const pt_params* params, const pt_adaptive* ad,
+                           float* out, const pt_moments* mom, int32_t* spp_out, int out_is_device,
+                           pt_adaptive_stats* st);
 
 /* pt_ctx_render followed by gamma_correct + save_png quantisation on the device
  * (image.h:41-55): out receives rows*W*3 bytes of this part (row order as pt_ctx_render;

@@ -188,4 +188,27 @@ struct PathsLaunch {
 };
 int paths_launch(void* stream, const QueryScene& sc, const WalkPlan& plan, const PathsLaunch& l);
 
+// ---- per-pixel rounds of pt_ctx_render_adaptive (pt_adaptive.hip; the host loop is in pt_kernel.hip) ----
+// All on `stream` (a hipStream_t), device pointers, no synchronisation. Lists hold part-local pixel indices.
+// paths_plan for the kernel fed from a list; `items`: listed pixels x samples of the largest launch.
+int adaptive_plan(const QueryScene& sc, size_t lds_usable, int num_cus, int depth, int64_t items, WalkPlan& plan);
+// Samples [s_begin, s_begin + l.spp) of the l.m pixels of `list`, traced as a render traces them
+// (camera_ray; cam, prm and shape as the render's): record j of l.slab is sample s_begin + j / l.m
+// of pixel list[j % l.m]. l.org, l.dir, l.states and l.ray_base are not read.
+int adaptive_launch(void* stream, const QueryScene& sc, const WalkPlan& plan, const PathsLaunch& l, const int32_t* list,
+                    int32_t s_begin, const pt_camera* cam, const pt_params* prm, const PartShape& shape);
+// The m pixels of `prev` (nullptr: pixels 0..m-1) that miss the criterion (pt_moments.h) after n
+// samples -> `list` (another buffer of m entries, order unspecified), their number -> *count
+// (zeroed here); spp[q] = n for those that meet it. mom: the context's S and Q over npix pixels.
+int adaptive_compact(void* stream, const int32_t* prev, int32_t m, const double* mom, int32_t npix, int32_t n, float rel,
+                     float abs_tol, int32_t* list, unsigned long long* count, int32_t* spp);
+// spp[list[i]] = n for i < m (list nullptr: spp[i] = n).
+int adaptive_fill_spp(void* stream, const int32_t* list, int32_t m, int32_t n, int32_t* spp);
+// A launch's slab (c samples of the m listed pixels) added in sample order to the pixels' float32
+// sums (accum, planes of npix) and double sums (mom); n_new > 0: out[q] = sum / n_new as well.
+int adaptive_accumulate(void* stream, const float* slab, const int32_t* list, int32_t m, int32_t c, float* accum,
+                        double* mom, float* out, int32_t npix, int32_t n_new);
+// The standard error of the mean of nval = 3 npix values, each with its pixel's n = spp[pixel].
+int adaptive_sem(void* stream, const double* mom, size_t nval, const int32_t* spp, float* sem);
+
 }  // namespace pt

@@ -83,28 +83,6 @@ static TraceKernel wide_kernel(int width, int fmt, bool lds_mats) {
                              : wide_kernel_t<4, kWideByte>(lds_mats);
 }
 
-// A pixel's running sums as slab_walk's accumulator (pt_trace.h) in a moments render: the image's
-// float32 sum (SumF32's) and, per channel beside it, S = sum of (double)r and Q = sum of
-// (double)r * (double)r (include/pt_hip.h: pt_moments; the product of two floats is exact in
-// double, every addition is rounded on its own). A +0 record (a slot the parallel walk pads
-// with) changes none of them.
-struct MomentSums {
-    float &x, &y, &z;
-    double sx, sy, sz, qx, qy, qz;
-    __device__ __forceinline__ void add(const float3 v) {
-        x += v.x;
-        y += v.y;
-        z += v.z;
-        const double dx = (double)v.x, dy = (double)v.y, dz = (double)v.z;
-        sx += dx;
-        sy += dy;
-        sz += dz;
-        qx += dx * dx;
-        qy += dy * dy;
-        qz += dz * dz;
-    }
-};
-
 // Running per-pixel sum in sample order (image.h:27-31 via render.h:84), then /spp
 // (image.h:37-40) on the last batch; output interleaved RGB rows of this part. The order of the
 // sum is slab_walk<true>'s (pt_trace.h): dense records, or a flagged slab's flagged ones.
@@ -418,6 +396,16 @@ struct pt_ctx {
     unsigned long long* d_mcount = nullptr;
     float* d_sem = nullptr;
     size_t sem_floats = 0;
+    // per-pixel rounds of pt_ctx_render_adaptive (pt_adaptive.hip): buffers of its own
+    int32_t* d_alist[2] = {nullptr, nullptr};  // the active list and the next one (part-local pixel indices)
+    size_t alist_ints[2] = {0, 0};
+    int32_t* d_aspp = nullptr;               // n_p per pixel
+    size_t aspp_ints = 0;
+    float* d_aslab = nullptr;                // dense radiance slab of one launch, [sample][listed pixel][rgb]
+    size_t aslab_floats = 0;
+    float* d_arec = nullptr;                 // path records, when they do not go to LDS
+    size_t arec_words = 0;
+    unsigned long long* d_actr = nullptr;    // work head, ray and runaway counters (4 x u64), then the list's count
     // progressive rendering: d_accum holds the running sum of prog_spp samples; prog_moments: the
     // sum is a moments sum (d_mom continues with it, over prog_npix pixels)
     bool prog_valid = false;
@@ -1268,8 +1256,9 @@ int moments_range(pt_ctx* c, const pt_camera* cam, const pt_params* prm, int32_t
 }
 
 // The context's moments to the caller's arrays (device or host pointers): S and Q are copies of
-// d_mom's halves, sem is computed from them. Synchronous.
-int moments_export(pt_ctx* c, const pt_moments* mom, int is_device) {
+// d_mom's halves, sem is computed from them with n = prog_spp, or with each pixel's own n
+// (d_spp, after per-pixel rounds). Synchronous.
+int moments_export(pt_ctx* c, const pt_moments* mom, int is_device, const int32_t* d_spp = nullptr) {
     const size_t nval = 3 * (size_t)c->prog_npix;
     if (!mom || nval == 0) return PT_OK;
     const hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
@@ -1279,8 +1268,12 @@ int moments_export(pt_ctx* c, const pt_moments* mom, int is_device) {
         if (!is_device)
             if (int rc = ensure(&c->d_sem, &c->sem_floats, nval)) return rc;
         float* dst = is_device ? mom->sem : c->d_sem;
-        hipLaunchKernelGGL(pt_moments_sem_kernel, dim3((unsigned)((nval + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
-                           c->d_mom, nval, c->prog_spp, dst);
+        if (d_spp) {
+            if (int rc = adaptive_sem(c->stream, c->d_mom, nval, d_spp, dst)) return rc;
+        } else {
+            hipLaunchKernelGGL(pt_moments_sem_kernel, dim3((unsigned)((nval + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                               c->stream, c->d_mom, nval, c->prog_spp, dst);
+        }
         if (!is_device) HIP_TRY(hipMemcpyAsync(mom->sem, dst, nval * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1415,7 +1408,8 @@ void pt_ctx_destroy(pt_ctx* c) {
                     (void*)c->d_accum, (void*)c->d_out, (void*)c->d_ctr, (void*)c->d_stamps, (void*)c->d_rgb8, (void*)c->d_thr, (void*)c->d_xstack,
                     (void*)c->d_rank_tri, (void*)c->d_qstack, (void*)c->d_qbuf, (void*)c->d_qhits,
                     (void*)c->d_tslab, (void*)c->d_trec, (void*)c->d_tbuf, (void*)c->d_tstates, (void*)c->d_tctr,
-                    (void*)c->d_gtab, (void*)c->d_gmats, (void*)c->d_gbuf, (void*)c->d_mom, (void*)c->d_mcount, (void*)c->d_sem})
+                    (void*)c->d_gtab, (void*)c->d_gmats, (void*)c->d_gbuf, (void*)c->d_mom, (void*)c->d_mcount, (void*)c->d_sem,
+                    (void*)c->d_alist[0], (void*)c->d_alist[1], (void*)c->d_aspp, (void*)c->d_aslab, (void*)c->d_arec, (void*)c->d_actr})
         if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -2153,6 +2147,214 @@ int pt_ctx_trace_grad(pt_ctx* c, const float* origins, const float* dirs, int64_
     if (h_ctr[3] != 0)
         return set_error(PT_E_RUNAWAY, "%llu specular rejection loops hit the %d-iteration bound", h_ctr[3],
                          kMaxSpecularIters);
+    return PT_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- adaptive sampling
+// pt_ctx_render_converge whose later rounds go only to the pixels that still miss the criterion:
+// dense rounds through moments_range, then per-pixel rounds through the kernels of pt_adaptive.hip
+// (the binary walk of pt_ctx_trace fed with the render's camera rays of a compacted pixel list).
+namespace {
+
+// The active fraction below which a per-pixel round pays (pt_adaptive::sparse_below = 0), by the
+// kernel family of the dense rounds: 0.8 of the rate of the binary walk over the rate of the
+// render's own kernel, both measured inside this call at 1024^2, depth 5 (scripts/adaptive_bench.py,
+// profiles/adaptive): flat 10.4 / 53.7 Gray/s = 0.194 on Cornell (0.242 with
+// emission on every surface: the lower one counts), wide 1.36 / 13.1 = 0.104 on the 99k mesh. A
+// scene whose render already runs the binary walk was not measured: §3.13's ratio of about 1.
+float default_sparse_below(int kernel_path) {
+    switch (kernel_path) {
+        case PT_PATH_FLAT_RTC:
+        case PT_PATH_FLAT_TABLE:
+        case PT_PATH_FLAT_TABLE_FAST: return 0.155f;
+        case PT_PATH_WIDE: return 0.083f;
+        default: return 0.8f;
+    }
+}
+
+// The per-pixel rounds from boundary n on (the switch included): the pixels that miss the criterion
+// at n are listed, the others frozen; rounds over the list until it holds at most max_unconverged
+// pixels or n reaches max_spp. dst: the device image (rows*W*3). S: rounds, samples, rays, times
+// and launches are added; unconverged and max_spp are set.
+int adaptive_rounds(pt_ctx* c, const pt_camera* cam, const pt_params* prm, const pt_converge* cv, int32_t n, float* dst,
+                    pt_adaptive_stats& S, int* runaway) {
+    PartShape shape;
+    int rc;
+    if ((rc = part_shape(cam, prm, PT_MAX_DEPTH, &shape))) return rc;
+    const int32_t npix = shape.npix;
+    c->prog_valid = false;  // the running sum is no longer one of a uniform sample count
+    for (int k = 0; k < 2; k++)
+        if ((rc = ensure(&c->d_alist[k], &c->alist_ints[k], (size_t)npix))) return rc;
+    if ((rc = ensure(&c->d_aspp, &c->aspp_ints, (size_t)npix))) return rc;
+    if (!c->d_actr) HIP_TRY(hipMalloc((void**)&c->d_actr, 5 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(c->d_actr, 0, 5 * sizeof(unsigned long long), c->stream));
+    unsigned long long* d_count = c->d_actr + 4;
+    EventPair ev, ev2;
+    HIP_TRY(hipEventCreate(&ev.a));
+    HIP_TRY(hipEventCreate(&ev.b));
+    HIP_TRY(hipEventCreate(&ev2.a));
+    // the unconverged pixels of `prev` (m of them; nullptr: the part) after n samples -> d_alist[to]; 8 bytes read back
+    auto compact = [&](const int32_t* prev, int32_t m, int32_t n_at, int to, int64_t* left) -> int {
+        unsigned long long h = 0;
+        HIP_TRY(hipEventRecord(ev.a, c->stream));
+        if (int crc = adaptive_compact(c->stream, prev, m, c->d_mom, npix, n_at, cv->rel, cv->abs, c->d_alist[to], d_count,
+                                       c->d_aspp))
+            return crc;
+        HIP_TRY(hipEventRecord(ev.b, c->stream));
+        HIP_TRY(hipMemcpyAsync(&h, d_count, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
+        S.reduce_ms += ms;
+        *left = (int64_t)h;
+        return PT_OK;
+    };
+    int cur = 0;
+    int64_t m = 0;
+    if ((rc = compact(nullptr, npix, n, cur, &m))) return rc;
+    S.samples = (int64_t)(npix - m) * n;
+
+    const QueryScene sc = query_scene(c);
+    PathsLaunch l{};
+    l.depth = prm->depth;
+    l.seed = prm->seed;
+    l.ctr = c->d_actr;
+    l.dark = c->dark ? 1 : 0;
+    l.force_exact = query_force_exact();
+    {
+        const float2* tab = nullptr;
+        if ((rc = theta_choice(c, &l.theta_lanes, &tab))) return rc;
+        l.theta_tab = tab;
+    }
+    // items (listed pixels x samples) per launch: the slab budget and the 2^31-item bound;
+    // PT_ADAPTIVE_CHUNK (test hook): the items themselves
+    int64_t items_max = std::min<int64_t>((1ll << 31) - 1, (int64_t)(batch_bytes_budget(c->device, false) / (3 * sizeof(float))));
+    if (const char* ac = hook_env("PT_ADAPTIVE_CHUNK"))
+        if (*ac) items_max = std::min<int64_t>(items_max, strtoll(ac, nullptr, 10));
+    items_max = std::max<int64_t>(items_max, 1);
+
+    while (m > cv->max_unconverged && n < cv->max_spp) {
+        const int32_t n_next = (int32_t)std::min<int64_t>(cv->step > 0 ? (int64_t)n + cv->step : 2 * (int64_t)n, cv->max_spp);
+        // a round is cut over samples first, then over listed pixels
+        const int64_t m_l = std::min<int64_t>(m, items_max);
+        const int64_t c_l = std::min<int64_t>(n_next - n, std::max<int64_t>(1, items_max / m_l));
+        WalkPlan plan;
+        if ((rc = adaptive_plan(sc, c->lds_usable, c->num_cus, prm->depth, m_l * c_l, plan))) return rc;
+        if (plan.stack_ints > 0 && (rc = ensure(&c->d_qstack, &c->qstack_ints, plan.stack_ints))) return rc;
+        if (plan.rec_words > 0 && (rc = ensure(&c->d_arec, &c->arec_words, 2 * plan.rec_words))) return rc;
+        if ((rc = ensure(&c->d_aslab, &c->aslab_floats, 3 * (size_t)(m_l * c_l)))) return rc;
+        l.slab = c->d_aslab;
+        l.gstack = c->d_qstack;
+        l.grec = plan.rec_words > 0 ? c->d_arec : nullptr;
+        for (int64_t a0 = 0; a0 < m; a0 += m_l) {
+            const int32_t* list = c->d_alist[cur] + a0;
+            l.m = (int32_t)std::min<int64_t>(m_l, m - a0);
+            for (int64_t s0 = n; s0 < n_next; s0 += c_l) {
+                l.spp = (int32_t)std::min<int64_t>(c_l, n_next - s0);
+                HIP_TRY(hipMemsetAsync(c->d_actr, 0, sizeof(unsigned long long), c->stream));  // work head only
+                HIP_TRY(hipEventRecord(ev.a, c->stream));
+                if ((rc = adaptive_launch(c->stream, sc, plan, l, list, (int32_t)s0, cam, prm, shape))) return rc;
+                HIP_TRY(hipEventRecord(ev.b, c->stream));
+                if ((rc = adaptive_accumulate(c->stream, c->d_aslab, list, l.m, l.spp, c->d_accum, c->d_mom, dst, npix,
+                                              s0 + l.spp == n_next ? n_next : 0)))
+                    return rc;
+                HIP_TRY(hipEventRecord(ev2.a, c->stream));
+                HIP_TRY(hipStreamSynchronize(c->stream));
+                float ms = 0;
+                HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
+                S.kernel_ms += ms;
+                S.sparse_kernel_ms += ms;
+                HIP_TRY(hipEventElapsedTime(&ms, ev.b, ev2.a));
+                S.reduce_ms += ms;
+                S.sparse_launches++;
+            }
+        }
+        int64_t left = 0;
+        if ((rc = compact(c->d_alist[cur], (int32_t)m, n_next, 1 - cur, &left))) return rc;
+        S.samples += (m - left) * n_next;
+        cur = 1 - cur;
+        m = left;
+        n = n_next;
+        S.rounds++;
+    }
+    // the pixels still listed keep the last boundary
+    if ((rc = adaptive_fill_spp(c->stream, c->d_alist[cur], (int32_t)m, n, c->d_aspp))) return rc;
+    S.samples += m * n;
+    S.unconverged = m;
+    S.max_spp = n;
+    unsigned long long h_ctr[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h_ctr, c->d_actr, sizeof(h_ctr), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    S.sparse_rays = h_ctr[1];
+    S.rays += h_ctr[1];
+    if (h_ctr[3] != 0) *runaway = PT_E_RUNAWAY;
+    return PT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pt_ctx_render_adaptive(pt_ctx* c, const pt_camera* cam, const pt_params* prm, const pt_adaptive* ad, float* out,
+                           const pt_moments* mom, int32_t* spp_out, int out_is_device, pt_adaptive_stats* as) {
+    const auto t_start = std::chrono::steady_clock::now();
+    if (!c || !cam || !prm || !ad) return set_error(PT_E_ARG, "pt_ctx_render_adaptive: NULL argument");
+    const pt_converge* cv = &ad->conv;
+    if (!tolerances_ok(cv->rel, cv->abs))
+        return set_error(PT_E_ARG, "pt_ctx_render_adaptive: rel and abs must be >= 0 and not both 0");
+    if (cv->min_spp < 2 || cv->max_spp < cv->min_spp || cv->step < 0 || cv->max_unconverged < 0)
+        return set_error(PT_E_ARG, "pt_ctx_render_adaptive: needs 2 <= min_spp <= max_spp, step >= 0, max_unconverged >= 0");
+    if (ad->sparse_below != ad->sparse_below) return set_error(PT_E_ARG, "pt_ctx_render_adaptive: sparse_below is NaN");
+    pt_adaptive_stats S{};
+    int runaway = PT_OK;
+    float below = ad->sparse_below;
+    bool sparse = false;
+    int32_t n = cv->min_spp;
+    // dense rounds, as pt_ctx_render_converge's: on a device image they write it in place
+    for (int32_t done = 0;;) {
+        pt_stats st{};
+        const int rc = moments_range(c, cam, prm, done, n - done, out_is_device ? out : nullptr, out_is_device, &st);
+        if (rc && rc != PT_E_RUNAWAY) return rc;
+        if (rc) runaway = rc;
+        S.rays += st.rays;
+        S.kernel_ms += st.kernel_ms;
+        S.reduce_ms += st.reduce_ms;
+        if (int urc = unconverged_count(c, cv->rel, cv->abs, &S.unconverged, nullptr, 0, &S.reduce_ms)) return urc;
+        S.rounds++;
+        S.dense_rounds++;
+        S.max_spp = done = n;
+        if (below == 0.0f) below = default_sparse_below(st.kernel_path);
+        if (S.unconverged <= cv->max_unconverged || n >= cv->max_spp) break;
+        if (below > 0.0f && (double)S.unconverged <= (double)below * (double)c->prog_npix) {
+            sparse = true;
+            break;
+        }
+        n = (int32_t)std::min<int64_t>(cv->step > 0 ? (int64_t)n + cv->step : 2 * (int64_t)n, cv->max_spp);
+    }
+    const int npix = c->prog_npix;
+    S.samples = (int64_t)npix * n;
+    if (sparse) {
+        float* dst = out_is_device && out ? out : c->d_out;
+        if (int rc = adaptive_rounds(c, cam, prm, cv, n, dst, S, &runaway)) return rc;
+    }
+    if (out && !out_is_device && npix > 0)
+        HIP_TRY(hipMemcpyAsync(out, c->d_out, 3 * (size_t)npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (spp_out && npix > 0) {
+        if (!sparse) {  // every pixel received the last boundary's samples
+            if (int rc = ensure(&c->d_aspp, &c->aspp_ints, (size_t)npix)) return rc;
+            if (int rc = adaptive_fill_spp(c->stream, nullptr, npix, n, c->d_aspp)) return rc;
+        }
+        HIP_TRY(hipMemcpyAsync(spp_out, c->d_aspp, (size_t)npix * sizeof(int32_t),
+                               out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int xrc = moments_export(c, mom, out_is_device, sparse ? c->d_aspp : nullptr)) return xrc;
+    S.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    if (as) *as = S;
+    if (runaway)
+        return set_error(PT_E_RUNAWAY, "specular rejection loops hit the %d-iteration bound during the rounds", kMaxSpecularIters);
     return PT_OK;
 }
 

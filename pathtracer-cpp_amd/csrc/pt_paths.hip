@@ -3,7 +3,9 @@
 //
 //   pt_paths_kernel<kLdsScene, kLdsStack, kLdsRec>  one path per lane: intersect_tree, shade and
 //                                                   finish_path of pt_trace.h, fed from a ray
-//                                                   buffer instead of camera_ray
+//                                                   buffer instead of camera_ray (the loop itself:
+//                                                   paths_body, pt_paths.h, shared with the
+//                                                   per-pixel rounds of pt_adaptive.hip)
 //
 // A work item is (ray, sample); the items of a launch over m rays are numbered sample-major
 // (item j -> sample j / m, ray j % m), so consecutive lanes load consecutive rays and item j's
@@ -39,106 +41,16 @@
 
 #include <algorithm>
 
-#include "pt_launch.h"
-#include "pt_raygate.h"
-#include "pt_trace.h"
+#include "pt_paths.h"
 
 namespace pt {
 
 static_assert(kSpecularIterBound == kMaxSpecularIters, "host and device bound of the specular rejection loop");
 
-struct PathArgs {
-    const float* __restrict__ org;        // m x 3
-    const float* __restrict__ dir;        // m x 3
-    const uint32_t* __restrict__ states;  // m x spp LCG states [ray][sample], or nullptr
-    int* __restrict__ gstack;             // !kLdsStack: [grid][rows][kBlock]
-    int* __restrict__ grec_tri;           // !kLdsRec: [grid][rec][kBlock]
-    float* __restrict__ grec_cos;
-    uint32_t m;                           // rays of this launch
-    uint32_t spp;
-    uint32_t ray_base;                    // index in the call of this launch's first ray (default seeding)
-    int rows;                             // stack rows
-    int force_exact;                      // PT_FORCE_EXACT_SLAB: never the IEEE min/max slab form
-};
-
+// The loop (paths_body, pt_paths.h) over the caller's ray buffer.
 template <bool kLdsScene, bool kLdsStack, bool kLdsRec>
 __global__ __launch_bounds__(kBlock) void pt_paths_kernel(TraceArgs A, PathArgs P) {
-    extern __shared__ float4 lds4[];
-    const int tid = threadIdx.x;
-    const int lane = tid & (kWave - 1);
-    const float4* __restrict__ nodes = A.nodes;
-    const float4* __restrict__ tris = A.tris;
-    const float4* __restrict__ mats = A.mats;
-    const int scene4 = kLdsScene ? A.num_node4 + A.num_tri4 + A.num_mat4 : 0;
-    if (kLdsScene) {
-        float4* s_nodes = lds4;
-        float4* s_tris = lds4 + A.num_node4;
-        float4* s_mats = s_tris + A.num_tri4;
-        for (int i = tid; i < A.num_node4; i += kBlock) s_nodes[i] = A.nodes[i];
-        for (int i = tid; i < A.num_tri4; i += kBlock) s_tris[i] = A.tris[i];
-        for (int i = tid; i < A.num_mat4; i += kBlock) s_mats[i] = A.mats[i];
-        __syncthreads();
-        nodes = s_nodes;
-        tris = s_tris;
-        mats = s_mats;
-    }
-    int* const lds_stk = reinterpret_cast<int*>(lds4 + scene4);
-    int* const lds_rec = lds_stk + (kLdsStack ? P.rows * kBlock : 0);
-    int* __restrict__ stk = kLdsStack ? lds_stk : P.gstack + (size_t)blockIdx.x * P.rows * kBlock;
-    int* __restrict__ rec_tri = kLdsRec ? lds_rec : P.grec_tri + (size_t)blockIdx.x * A.rec_size * kBlock;
-    float* __restrict__ rec_cos = kLdsRec ? reinterpret_cast<float*>(lds_rec + A.rec_size * kBlock)
-                                          : P.grec_cos + (size_t)blockIdx.x * A.rec_size * kBlock;
-
-    bool alive = true;     // the pool may still hold items for this lane
-    bool active = false;   // the lane has a path in flight (item `item`)
-    bool nan_cos = false;  // its path recorded a non-finite cosine
-    uint32_t item = 0;
-    Lcg g{0};
-    v3 o{0, 0, 0}, d{0, 0, 1};
-    int k = 0;
-    unsigned long long n_rays = 0;  // this wave's segments (wave-uniform)
-    Pool pool = pool_start(A);
-
-    while (true) {
-        const bool need = alive && !active;
-        if (__any(need)) {
-            claim_item(A, lane, need, pool, alive, item);
-            if (need && alive) {  // item < total_items = m * spp
-                const uint32_t sm = fdiv(item, A.div_npix), i = item - sm * P.m;
-                o = v3{P.org[3 * (size_t)i], P.org[3 * (size_t)i + 1], P.org[3 * (size_t)i + 2]};
-                d = v3{P.dir[3 * (size_t)i], P.dir[3 * (size_t)i + 1], P.dir[3 * (size_t)i + 2]};
-                g.s = P.states ? P.states[(size_t)i * P.spp + sm] : pt_sample_seed(P.ray_base + i, sm, A.seed);
-                k = 0;
-                nan_cos = false;
-                active = true;
-            }
-        }
-        if (!__any(active)) break;
-
-        // ---- BVH::intersect (bvh.h:156-183)
-        float t = 0.0f;
-        int hit = -1;
-        n_rays += (unsigned long long)__popcll(__ballot(active));
-        const v3 inv{rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z)};  // bvh.h:157
-        const bool fast = !P.force_exact && __all(!active || query_ray_bounded(o, inv));
-        if (active)
-            hit = fast ? intersect_tree<true>(nodes, tris, stk, tid, o, d, inv, t)
-                       : intersect_tree<false>(nodes, tris, stk, tid, o, d, inv, t);
-        bool end = false;
-        v3 L{0.0f, 0.0f, 0.0f};
-        if (active) {
-            end = shade(A, mats, tris, rec_tri, rec_cos, tid, hit, t, g, o, d, k, L);
-            // the recorded cosine n . d' is finite exactly when the new direction is (|n| = 1)
-            if (!end) nan_cos = nan_cos || !all_finite(d);
-        }
-        if (__any(end && nan_cos)) {
-            if (end) finish_path<int, false, true, false>(A, mats, rec_tri, rec_cos, tid, k, L, item);
-        } else if (end) {
-            finish_path<int>(A, mats, rec_tri, rec_cos, tid, k, L, item);
-        }
-        if (end) active = false;
-    }
-    count_rays_wave(A, lane, n_rays);
+    paths_body<BufferRays, kLdsScene, kLdsStack, kLdsRec>(A, P);
 }
 
 namespace {
@@ -166,13 +78,9 @@ int paths_plan(const QueryScene& sc, size_t lds_usable, int num_cus, int depth, 
                      plan, "trace");
 }
 
-int paths_launch(void* stream, const QueryScene& sc, const WalkPlan& plan, const PathsLaunch& l) {
+void paths_args(const QueryScene& sc, const WalkPlan& plan, const PathsLaunch& l, int grid, TraceArgs& A, PathArgs& P) {
     const unsigned long long total = (unsigned long long)l.m * (unsigned long long)l.spp;
-    if (l.m <= 0 || l.spp <= 0 || l.depth <= 0 || total >= (1ull << 31))
-        return set_error(PT_E_ARG, "trace launch of %d rays x %d samples, depth %d", l.m, l.spp, l.depth);
-    const int grid = (int)std::min<unsigned long long>((unsigned long long)plan.grid, (total + kBlock - 1) / kBlock);
     // every field shade, finish_path and claim_item read, as fill_trace_args (pt_kernel.hip) fills them
-    TraceArgs A;
     memset(&A, 0, sizeof(A));
     A.nodes = reinterpret_cast<const float4*>(sc.nodes);
     A.tris = reinterpret_cast<const float4*>(sc.tris);
@@ -204,7 +112,7 @@ int paths_launch(void* stream, const QueryScene& sc, const WalkPlan& plan, const
     A.static_base = pool.static_base;
     A.acc_chunks = 0;            // no fused accumulation: the sum is a pass of its own
 
-    PathArgs P{};
+    P = PathArgs{};
     P.org = l.org;
     P.dir = l.dir;
     P.states = l.states;
@@ -216,6 +124,16 @@ int paths_launch(void* stream, const QueryScene& sc, const WalkPlan& plan, const
     P.ray_base = l.ray_base;
     P.rows = plan.rows;
     P.force_exact = l.force_exact;
+}
+
+int paths_launch(void* stream, const QueryScene& sc, const WalkPlan& plan, const PathsLaunch& l) {
+    const unsigned long long total = (unsigned long long)l.m * (unsigned long long)l.spp;
+    if (l.m <= 0 || l.spp <= 0 || l.depth <= 0 || total >= (1ull << 31))
+        return set_error(PT_E_ARG, "trace launch of %d rays x %d samples, depth %d", l.m, l.spp, l.depth);
+    const int grid = (int)std::min<unsigned long long>((unsigned long long)plan.grid, (total + kBlock - 1) / kBlock);
+    TraceArgs A;
+    PathArgs P;
+    paths_args(sc, plan, l, grid, A, P);
     hipLaunchKernelGGL(paths_kernel(plan.lds_scene, plan.lds_stack, plan.lds_rec), dim3(grid), dim3(kBlock), plan.lds_bytes,
                        (hipStream_t)stream, A, P);
     const hipError_t e = hipGetLastError();

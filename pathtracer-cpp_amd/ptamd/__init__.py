@@ -558,6 +558,43 @@ class Renderer:
         self._mom_pixels = rows * W
         return img, res, cs.as_dict()
 
+    def render_adaptive(self, camera: Camera, depth: int, rel: float, abs: float = 0.0, min_samples: int = 16,
+                        max_samples: int = 4096, step: int = 0, max_unconverged: int = 0, sparse_below: float = 0.0,
+                        seed: int = PT_SEED, part_index: int = 0, part_count: int = 1, band_rows: int = 1, out=None,
+                        want: Sequence[str] = _lib.pt_moments.NAMES):
+        """render_converge that spends its later rounds only on the pixels that still miss the
+        target (pt_ctx_render_adaptive). The round ends are render_converge's. At the first one
+        where at most sparse_below * pixels (and more than max_unconverged) miss the target, those
+        pixels become the active list and every other pixel is frozen with that sample count; from
+        then on only listed pixels are sampled and evaluated, and one that meets the target leaves
+        the list with the round's sample count. sparse_below = 0: the library's default for the
+        scene's kernel; < 0: never (the call is render_converge); >= 1: from the first round end.
+        Returns (img, moments, spp, info). spp (rows, W) int32 is each pixel's sample count n_p;
+        a pixel of img holds the bits of render() with n_p samples, moments "sum" and "sumsq" are
+        over its n_p samples and "sem" uses n_p. info = {"rounds", "dense_rounds", "max_spp",
+        "sparse_launches", "unconverged", "samples" (the sum of n_p), "rays", "sparse_rays",
+        "kernel_ms", "reduce_ms", "total_ms", "sparse_kernel_ms"}. After per-pixel rounds the context holds no running
+        moments sum (unconverged() and a render_moments continuation raise PTError); without them
+        the state is render_converge's. `out`: None (numpy results) or a torch float32 tensor on
+        this context's device, written in place; moments and spp are then tensors there."""
+        W, H = camera.res
+        rows = self.part_rows(H, part_index, part_count, band_rows)
+        img, res, img_ptr, mom, dev = self._moments_io(rows, W, want, out)
+        if dev:
+            import torch
+            spp = torch.empty((rows, W), dtype=torch.int32, device=out.device)
+            spp_ptr = C.c_void_p(spp.data_ptr())
+        else:
+            spp = np.empty((rows, W), dtype=np.int32)
+            spp_ptr = C.c_void_p(spp.ctypes.data)
+        prm = _lib.pt_params(0, depth, seed, part_index, part_count, band_rows, 0, 0)
+        ad = _lib.pt_adaptive(_lib.pt_converge(rel, abs, min_samples, max_samples, step, max_unconverged), sparse_below)
+        st = _lib.pt_adaptive_stats()
+        check(lib().pt_ctx_render_adaptive(self.h, C.byref(camera.c), C.byref(prm), C.byref(ad), img_ptr, C.byref(mom),
+                                           spp_ptr, dev, C.byref(st)))
+        self._mom_pixels = rows * W
+        return img, res, spp, st.as_dict()
+
     def render_rgb8(self, camera: Camera, samples: int, depth: int, gamma: float = 2.2, flip: bool = True,
                     seed: int = PT_SEED, part_index: int = 0, part_count: int = 1, band_rows: int = 1, out=None,
                     batch_spp: int = 0, samples_per_item: int = 0):

@@ -33,6 +33,7 @@ EXPORTED = (
     "pt_bvh_trace_grad", "pt_ctx_trace_grad",
     "pt_debug_emit_reject", "pt_debug_emit_box", "pt_debug_ctx_emit_reject", "pt_debug_emit_slab_reject", "pt_debug_ray_stack",
     "pt_ctx_render_moments", "pt_moments_unconverged", "pt_ctx_unconverged", "pt_ctx_render_converge",
+    "pt_ctx_render_adaptive",
 )
 PT_MAX_DEVICES = 16
 
@@ -140,6 +141,21 @@ class pt_converge(C.Structure):
 class pt_converge_stats(C.Structure):
     _fields_ = [("spp", C.c_int32), ("rounds", C.c_int32), ("unconverged", C.c_int64), ("rays", C.c_uint64),
                 ("kernel_ms", C.c_double), ("reduce_ms", C.c_double), ("total_ms", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class pt_adaptive(C.Structure):
+    """Adaptive sampling (include/pt_hip.h): pt_converge and the active fraction at which the rounds go per pixel."""
+    _fields_ = [("conv", pt_converge), ("sparse_below", C.c_float)]
+
+
+class pt_adaptive_stats(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("dense_rounds", C.c_int32), ("max_spp", C.c_int32),
+                ("sparse_launches", C.c_int32), ("unconverged", C.c_int64), ("samples", C.c_int64),
+                ("rays", C.c_uint64), ("sparse_rays", C.c_uint64), ("kernel_ms", C.c_double),
+                ("reduce_ms", C.c_double), ("total_ms", C.c_double), ("sparse_kernel_ms", C.c_double)]
 
     def as_dict(self) -> dict:
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -258,6 +274,9 @@ def lib() -> C.CDLL:
             L.pt_ctx_unconverged.argtypes = [P, C.c_float, C.c_float, C.POINTER(C.c_int64), P, C.c_int]
             L.pt_ctx_render_converge.argtypes = [P, C.POINTER(pt_camera), C.POINTER(pt_params), C.POINTER(pt_converge), P,
                                                  C.POINTER(pt_moments), C.c_int, C.POINTER(pt_converge_stats)]
+        if hasattr(L, "pt_ctx_render_adaptive"):  # absent from older builds used in A/B runs
+            L.pt_ctx_render_adaptive.argtypes = [P, C.POINTER(pt_camera), C.POINTER(pt_params), C.POINTER(pt_adaptive), P,
+                                                 C.POINTER(pt_moments), P, C.c_int, C.POINTER(pt_adaptive_stats)]
         if hasattr(L, "pt_debug_rccl_failover"):  # test hooks (absent from older builds used in A/B runs)
             L.pt_debug_rccl_failover.argtypes = [C.c_int32, C.c_int32, P]
         if hasattr(L, "pt_debug_rtc_cache"):
