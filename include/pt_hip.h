@@ -445,6 +445,121 @@ typedef struct pt_aov {
 int pt_ctx_render_aov(pt_ctx* ctx, const pt_camera* cam, const pt_params* params, int32_t sample,
                       const pt_aov* out, int out_is_device, pt_query_stats* stats);
 
+/* ---- variance-guided a-trous denoiser over AOVs and sample moments -----------------
+ * An edge-avoiding a-trous wavelet filter (the spatial part of SVGF) over a whole image of W x H
+ * pixels, rows in pt_ctx_render's order, guided by the first hit's channels and, optionally, by
+ * the variance of the mean. The result is defined bit for bit: only + - * / sqrt and comparisons
+ * in float32, each rounded on its own (no fused multiply-add, no exp), so the host form and the
+ * device form return the same bits.
+ *
+ * Inputs. color: 3 floats per pixel. var (optional): 3 floats per pixel, the variance of color
+ * as a mean (pt_moments_variance). Guides: normal, t, tri and emission are pt_aov's channels of
+ * the same names; position (3 floats) is the first hit's point, per component o + d * t (one
+ * multiplication, then one addition, as trace() forms its hit point). All five are required.
+ * A pixel's class: 0 for a miss (tri < 0), 2 for a hit with any emission channel != 0, else 1.
+ *
+ * Pass i = 0 .. passes-1 runs with stride s = 2^i and takes (c, v) to (c', v') for every pixel
+ * p = (x, y). Every dot product is ((a.x*b.x) + (a.y*b.y)) + (a.z*b.z).
+ *  1. l(q) = ((0.25f*c_r) + (0.5f*c_g)) + (0.25f*c_b).
+ *  2. With var only: vt_ch = the 3x3 mean of v_ch around p (stride 1), weights g = [1/4, 1/2, 1/4]
+ *     per axis, rows j the outer loop and columns k the inner, both ascending, in-image taps only:
+ *     acc += (g_j*g_k) * v, wacc += g_j*g_k, vt = acc / wacc.
+ *     sig_p = ((0.25f*sqrtf(vt_r)) + (0.5f*sqrtf(vt_g))) + (0.25f*sqrtf(vt_b));
+ *     den_p = (sigma_l*sig_p) + eps.
+ *  3. tau_p = sigma_z * t_p.
+ *  4. Taps: j = -2..2 outer, k = -2..2 inner, q = (x + k*s, y + j*s); a tap outside the image is
+ *     skipped. h = [1/16, 1/4, 3/8, 1/4, 1/16], hh = h_j * h_k (exact). The centre tap has w = 1.
+ *     For every other tap: class_q != class_p skips it. class_p == 0: wg = 1; otherwise
+ *         dn = n_p . n_q, set to 0 unless dn > 0, then squared normal_pow_log2 times (dn = dn*dn);
+ *         dl = | n_p . (X_q - X_p) |  (the difference per component first);
+ *         wz = (dl < tau_p) ? (tau_p - dl) / tau_p : 0;   wg = dn * wz.
+ *     Without var wl = 1; with it xl = |l_p - l_q| / den_p and wl = 1 / (1 + xl*xl).
+ *     w = wg * wl; unless w > 0 the tap is skipped (a NaN skips it too). Then, per channel,
+ *         kq = hh * w;  A_ch += kq * c_ch(q);  B_ch += (kq*kq) * v_ch(q);  Wsum += kq
+ *     (A, B and Wsum start at +0; B only with var).
+ *  5. c'_ch = A_ch / Wsum; v'_ch = B_ch / (Wsum*Wsum). The centre tap keeps Wsum >= 9/64.
+ * The guides, tau and the classes are those of the input for every pass.
+ *
+ * Consequences. With var, a NaN or infinite colour of a neighbour never enters another pixel's
+ * sum (its wl is NaN or 0); without var the luminance does not gate, only the guides do. A NaN
+ * centre stays NaN. A pixel whose prefiltered variance vt is negative or NaN in a channel keeps
+ * its centre tap only. A +inf variance (n < 2) makes every luminance weight of that pixel 1
+ * (or NaN, hence skipped, for an infinite or NaN neighbour). First-hit guides cannot see edges
+ * inside a mirror's reflection: those are blurred.
+ *
+ * Passes ping-pong between two buffers of the implementation; out (W*H*3) and var_out (optional,
+ * W*H*3, only with var; else PT_E_ARG) receive the last pass's result and may alias color and var. */
+typedef struct pt_denoise_guides {
+    const float* normal;         /* 3 floats per pixel */
+    const float* t;              /* 1 float  */
+    const int32_t* tri;          /* 1 int32  */
+    const float* emission;       /* 3 floats */
+    const float* position;       /* 3 floats: o + d * t per component */
+} pt_denoise_guides;
+
+/* A 0 selects the default, so the values in effect are passes 1..8, normal_pow_log2 1..10 and
+ * positive floats; a negative or NaN value, passes > 8 or normal_pow_log2 > 10 is PT_E_ARG.
+ * A NULL pt_denoise_params selects every default. */
+typedef struct pt_denoise_params {   /* 20 bytes */
+    int32_t passes;              /* 0 (default: 5) or 1..8 */
+    float sigma_l;               /* > 0, default 1: luminance tolerance in standard deviations */
+    float sigma_z;               /* > 0, default 0.01: plane-distance tolerance as a fraction of t_p */
+    int32_t normal_pow_log2;     /* 0 (default: 7, power 128) or 1..10: squarings of the normal dot product */
+    float eps;                   /* > 0, default 1e-6: added to the luminance denominator */
+} pt_denoise_params;
+
+#define PT_DENOISE_DIRECT 1      /* one pixel per lane, every tap read through L1/L2 */
+#define PT_DENOISE_LDS 2         /* a 32x16 tile and its halo staged in LDS (stride 1 only) */
+typedef struct pt_denoise_stats {    /* 96 bytes */
+    double kernel_ms;            /* pack and pass kernels (HIP events) */
+    double total_ms;             /* end-to-end wall time of the call   */
+    int32_t passes;              /* passes run */
+    int32_t launches;            /* kernel launches (pack + passes) */
+    int32_t form[8];             /* per pass i (stride 2^i): PT_DENOISE_DIRECT or PT_DENOISE_LDS; 0: not run */
+    float pass_ms[8];            /* per pass: its kernel's duration */
+    float pack_ms;               /* the pack kernel's duration */
+    int32_t reserved;
+} pt_denoise_stats;
+
+/* The variance of the mean from the sample moments (pt_moments: S = sum, Q = sumsq), per pixel
+ * and channel, in double, every operation rounded on its own:
+ *     m = (S*S)/n;  d = (Q - m)/(n - 1);  d = d > 0 ? d : 0;  var = (float)(d/n);  +inf for n < 2.
+ * n is `n` for every pixel, or with spp != NULL the pixel's own spp[q] (npix int32:
+ * pt_ctx_render_adaptive's spp_out; `n` is then ignored). This is not sem*sem: sem is rounded
+ * after its square root. sum, sumsq: npix*3 doubles; var_out: npix*3 floats. Host, no device. */
+int pt_moments_variance(const double* sum, const double* sumsq, int64_t npix, int32_t n, const int32_t* spp,
+                        float* var_out);
+/* The same by a kernel on the context's device; is_device != 0: every pointer is a device pointer. */
+int pt_ctx_moments_variance(pt_ctx* ctx, const double* sum, const double* sumsq, int64_t npix, int32_t n,
+                            const int32_t* spp, float* var_out, int is_device);
+
+/* The filter on the host (no device needed). W, H >= 1, W*H <= 2^30. */
+int pt_image_denoise(int32_t W, int32_t H, const float* color, const float* var, const pt_denoise_guides* guides,
+                     const pt_denoise_params* params, float* out, float* var_out);
+/* The filter on the context's device, bit-identical to pt_image_denoise. is_device != 0: color,
+ * var, the guides, out and var_out are device pointers on the context's device. Needs no scene,
+ * is synchronous and leaves a running sum as it is. stats is optional. */
+int pt_ctx_denoise(pt_ctx* ctx, int32_t W, int32_t H, const float* color, const float* var,
+                   const pt_denoise_guides* guides, const pt_denoise_params* params, float* out, float* var_out,
+                   int is_device, pt_denoise_stats* stats);
+
+typedef struct pt_denoised_stats {
+    double total_ms;             /* end-to-end wall time of the call */
+    double aov_ms, variance_ms;  /* the AOV kernel's and the position + variance kernels' durations */
+    pt_denoise_stats denoise;
+} pt_denoised_stats;
+/* Render and denoise on the device without a host round trip between the steps:
+ * pt_ctx_render_adaptive (params, adaptive); pt_ctx_render_aov of sample 0 at params->seed;
+ * position = o + d * t; pt_moments_variance with the per-pixel n_p; pt_ctx_denoise with var.
+ * Needs params->part_count <= 1 (else PT_E_ARG: rows dealt to other GPUs have no neighbours).
+ * out (W*H*3) is bit-identical to making the four calls by hand; noisy_out (optional, W*H*3)
+ * receives the unfiltered image and spp_out (optional, W*H int32) the n_p; out_is_device covers
+ * the three. render_stats (a pt_adaptive_stats) and stats are optional. Errors are reported as by
+ * the pieces; after PT_E_RUNAWAY of the render the filter still runs and the code is returned. */
+int pt_ctx_render_denoised(pt_ctx* ctx, const pt_camera* cam, const pt_params* params, const pt_adaptive* adaptive,
+                           const pt_denoise_params* denoise_params, float* out, float* noisy_out, int32_t* spp_out,
+                           int out_is_device, pt_adaptive_stats* render_stats, pt_denoised_stats* stats);
+
 /* ---- radiance along caller-supplied rays (trace(), render.h:36-61) ------------
  * rgb_out[3 i ..] = (sum over s of trace(bvh, o_i, d_i, depth)) / (float)spp: the sum runs in
  * float32 in sample order s = 0, 1, ... from +0 and is divided per channel (image.h:37-40); with

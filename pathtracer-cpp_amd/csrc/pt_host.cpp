@@ -26,6 +26,7 @@
 
 #include "pt_internal.h"
 #include "pt_math.h"
+#include "pt_denoise.h"
 #include "pt_moments.h"
 
 namespace pt {
@@ -1007,6 +1008,31 @@ int pack_scene(const pt_scene* s, PackedScene& out) {
 
 using namespace pt;
 
+// pt_denoise_params with the defaults filled in (a 0 selects one) and the arguments every form of
+// the filter checks (include/pt_hip.h). `who`: the entry point's name for the message.
+int pt::denoise_check(const char* who, int32_t W, int32_t H, const float* color, const float* var,
+                      const pt_denoise_guides* g, const pt_denoise_params* prm, const float* out, const float* var_out,
+                      DnParams* P) {
+    if (W <= 0 || H <= 0 || (int64_t)W * H > (1ll << 30))
+        return set_error(PT_E_ARG, "%s: image of %d x %d pixels", who, W, H);
+    if (!color || !out || !g) return set_error(PT_E_ARG, "%s: NULL argument", who);
+    if (!g->normal || !g->t || !g->tri || !g->emission || !g->position)
+        return set_error(PT_E_ARG, "%s: normal, t, tri, emission and position are all needed", who);
+    if (var_out && !var) return set_error(PT_E_ARG, "%s: var_out without var", who);
+    const pt_denoise_params d = prm ? *prm : pt_denoise_params{0, 0.0f, 0.0f, 0, 0.0f};
+    if (d.passes < 0 || d.passes > kDnMaxPasses) return set_error(PT_E_ARG, "%s: passes %d is not 0 (the default) or 1..8", who, d.passes);
+    if (d.normal_pow_log2 < 0 || d.normal_pow_log2 > kDnMaxPowLog2)
+        return set_error(PT_E_ARG, "%s: normal_pow_log2 %d is not 0 (the default) or 1..10", who, d.normal_pow_log2);
+    if (!(d.sigma_l >= 0.0f) || !(d.sigma_z >= 0.0f) || !(d.eps >= 0.0f))
+        return set_error(PT_E_ARG, "%s: sigma_l, sigma_z and eps must be positive (0: the default)", who);
+    P->passes = d.passes ? d.passes : 5;
+    P->npow = d.normal_pow_log2 ? d.normal_pow_log2 : 7;
+    P->sigma_l = d.sigma_l != 0.0f ? d.sigma_l : 1.0f;
+    P->sigma_z = d.sigma_z != 0.0f ? d.sigma_z : 0.01f;
+    P->eps = d.eps != 0.0f ? d.eps : 1e-6f;
+    return PT_OK;
+}
+
 extern "C" {
 
 int pt_abi_version(void) { return PT_ABI_VERSION; }
@@ -1780,6 +1806,57 @@ int pt_moments_unconverged(const double* sum, const double* sumsq, int64_t npix,
         if (mask) mask[q] = un ? 1 : 0;
     }
     *count = c;
+    return PT_OK;
+}
+
+// The variance of the mean from the moments (dn_variance, pt_denoise.h).
+int pt_moments_variance(const double* sum, const double* sumsq, int64_t npix, int32_t n, const int32_t* spp,
+                        float* var_out) {
+    if (npix < 0 || (npix > 0 && (!sum || !sumsq || !var_out))) return set_error(PT_E_ARG, "pt_moments_variance: bad arrays");
+    for (int64_t i = 0; i < 3 * npix; i++) var_out[i] = dn_variance(sum[i], sumsq[i], spp ? spp[i / 3] : n);
+    return PT_OK;
+}
+
+// The a-trous filter on the host: the loops of pt_denoise.hip's kernels over dn_pack and dn_pixel.
+int pt_image_denoise(int32_t W, int32_t H, const float* color, const float* var, const pt_denoise_guides* g,
+                     const pt_denoise_params* prm, float* out, float* var_out) {
+    DnParams P;
+    if (int rc = denoise_check("pt_image_denoise", W, H, color, var, g, prm, out, var_out, &P)) return rc;
+    const size_t npix = (size_t)W * H;
+    std::vector<DnRec> nt(npix), xc(npix), col[2], vr[2];
+    for (int b = 0; b < 2; b++) {
+        col[b].resize(npix);
+        if (var) vr[b].resize(npix);
+    }
+    for (size_t i = 0; i < npix; i++)
+        dn_pack(i, color, var, g->normal, g->t, g->tri, g->emission, g->position, P.sigma_z, nt.data(), xc.data(),
+                col[0].data(), var ? vr[0].data() : nullptr);
+    for (int pass = 0; pass < P.passes; pass++) {
+        const int from = pass & 1, s = 1 << pass;
+        const DnPlanes src{nt.data(), xc.data(), col[from].data(), var ? vr[from].data() : nullptr, W};
+        for (int y = 0; y < H; y++)
+            for (int x = 0; x < W; x++) {
+                const size_t i = (size_t)y * W + x;
+                DnRec c{0, 0, 0, 0}, v{0, 0, 0, 0};
+                if (var)
+                    dn_pixel<true>(src, W, H, x, y, s, P, c, v);
+                else
+                    dn_pixel<false>(src, W, H, x, y, s, P, c, v);
+                col[1 - from][i] = c;
+                if (var) vr[1 - from][i] = v;
+            }
+    }
+    const int last = P.passes & 1;
+    for (size_t i = 0; i < npix; i++) {
+        out[3 * i] = col[last][i].x;
+        out[3 * i + 1] = col[last][i].y;
+        out[3 * i + 2] = col[last][i].z;
+        if (var_out) {
+            var_out[3 * i] = vr[last][i].x;
+            var_out[3 * i + 1] = vr[last][i].y;
+            var_out[3 * i + 2] = vr[last][i].z;
+        }
+    }
     return PT_OK;
 }
 

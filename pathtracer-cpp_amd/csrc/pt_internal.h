@@ -211,4 +211,17 @@ int adaptive_accumulate(void* stream, const float* slab, const int32_t* list, in
 // The standard error of the mean of nval = 3 npix values, each with its pixel's n = spp[pixel].
 int adaptive_sem(void* stream, const double* mom, size_t nval, const int32_t* spp, float* sem);
 
+// ---- the a-trous denoiser (pt_denoise.h, pt_denoise.hip; the host form is in pt_host.cpp) ----
+struct DnParams;
+// The arguments every form checks, and pt_denoise_params with its defaults filled in (pt_host.cpp).
+int denoise_check(const char* who, int32_t W, int32_t H, const float* color, const float* var,
+                  const pt_denoise_guides* g, const pt_denoise_params* prm, const float* out, const float* var_out,
+                  DnParams* P);
+// The denoiser's scratch on the context's device, kept by the context and freed with it
+// (pt_kernel.hip): buffer `slot` (0 records and ping-pong, 1 a host-pointer call's staging,
+// 2 pt_ctx_render_denoised's images and guides) grown to `bytes`. Waits for the context's stream
+// to exist and selects its device.
+constexpr int kDnScratchSlots = 3;
+int ctx_scratch(pt_ctx* c, int slot, size_t bytes, void** out);
+
 }  // namespace pt

@@ -406,6 +406,9 @@ struct pt_ctx {
     float* d_arec = nullptr;                 // path records, when they do not go to LDS
     size_t arec_words = 0;
     unsigned long long* d_actr = nullptr;    // work head, ray and runaway counters (4 x u64), then the list's count
+    // the denoiser's scratch (pt_denoise.hip through ctx_scratch)
+    void* d_dn[kDnScratchSlots] = {};
+    size_t dn_bytes[kDnScratchSlots] = {};
     // progressive rendering: d_accum holds the running sum of prog_spp samples; prog_moments: the
     // sum is a moments sum (d_mom continues with it, over prog_npix pixels)
     bool prog_valid = false;
@@ -1411,6 +1414,8 @@ void pt_ctx_destroy(pt_ctx* c) {
                     (void*)c->d_gtab, (void*)c->d_gmats, (void*)c->d_gbuf, (void*)c->d_mom, (void*)c->d_mcount, (void*)c->d_sem,
                     (void*)c->d_alist[0], (void*)c->d_alist[1], (void*)c->d_aspp, (void*)c->d_aslab, (void*)c->d_arec, (void*)c->d_actr})
         if (p) (void)hipFree(p);
+    for (void* p : c->d_dn)
+        if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -2359,6 +2364,15 @@ int pt_ctx_render_adaptive(pt_ctx* c, const pt_camera* cam, const pt_params* prm
 }
 
 }  // extern "C"
+
+int pt::ctx_scratch(pt_ctx* c, int slot, size_t bytes, void** out) {
+    if (!c || slot < 0 || slot >= kDnScratchSlots) return set_error(PT_E_ARG, "ctx_scratch: bad argument");
+    if (int rc = ctx_ready(c)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = ensure_bytes(&c->d_dn[slot], &c->dn_bytes[slot], bytes, 1)) return rc;
+    *out = c->d_dn[slot];
+    return PT_OK;
+}
 
 void* pt::ctx_stream(pt_ctx* c) { return c && ctx_ready(c) == PT_OK ? (void*)c->stream : nullptr; }
 

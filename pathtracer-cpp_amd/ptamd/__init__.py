@@ -95,6 +95,19 @@ def _is_tensor(x) -> bool:
 GRAD_WANT = ("rgb", "color", "emit")
 
 
+def _own_device_tensors(device: int, *tensors) -> None:
+    """The rule of the device-pointer paths that read tensors torch may still be writing
+    (Renderer.denoise, moments_variance, render_denoised, aov(device=True)): every tensor is on
+    the context's device, and the work queued on torch's current stream of that device is
+    complete before the library's own stream (which does not order itself after torch's) touches
+    them. The library synchronises its stream before it returns, so torch may use the results at once."""
+    import torch
+    for x in tensors:
+        if x is not None and (not x.is_cuda or x.device.index != device):
+            raise ValueError(f"tensors must be on the context's device cuda:{device}")
+    torch.cuda.current_stream(device).synchronize()
+
+
 def _grad_want(want) -> Tuple[str, ...]:
     want = tuple(want)
     for k in want:
@@ -743,22 +756,153 @@ class Renderer:
 
     def aov(self, camera: Camera, sample: int = 0, seed: int = PT_SEED,
             channels: Sequence[str] = _lib.pt_aov.CHANNELS, part_index: int = 0, part_count: int = 1,
-            band_rows: int = 1):
+            band_rows: int = 1, device: bool = False):
         """First-hit channels of sample `sample` of this part's pixels (pt_ctx_render_aov): a
         dict of (rows, W) arrays for "t" (float32) and "tri" (int32), (rows, W, 3) for
         "normal", "albedo", "emission" and (rows, W, 6) for "ray" (o.xyz, d.xyz), rows in
-        render()'s order, + stats."""
+        render()'s order, + stats. device=True: torch tensors on this context's device, written
+        through device pointers."""
         W, H = camera.res
         rows = self.part_rows(H, part_index, part_count, band_rows)
         prm = _lib.pt_params(1, 1, seed, part_index, part_count, band_rows, 0, 0)
         res, aov = {}, _lib.pt_aov()
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
         for k in channels:
             w = _lib.pt_aov.WIDTH[k]  # KeyError: not a channel
-            res[k] = np.empty((rows, W) if w == 1 else (rows, W, w), dtype=np.int32 if k == "tri" else np.float32)
-            setattr(aov, k, res[k].ctypes.data)
+            shape = (rows, W) if w == 1 else (rows, W, w)
+            if device:
+                res[k] = torch.empty(shape, dtype=torch.int32 if k == "tri" else torch.float32, device=dev)
+                setattr(aov, k, res[k].data_ptr())
+            else:
+                res[k] = np.empty(shape, dtype=np.int32 if k == "tri" else np.float32)
+                setattr(aov, k, res[k].ctypes.data)
+        if device:
+            _own_device_tensors(self.device)  # the fresh tensors' memory may belong to work torch still has queued
         st = _lib.pt_query_stats()
-        check(lib().pt_ctx_render_aov(self.h, C.byref(camera.c), C.byref(prm), sample, C.byref(aov), 0, C.byref(st)))
+        check(lib().pt_ctx_render_aov(self.h, C.byref(camera.c), C.byref(prm), sample, C.byref(aov), int(device),
+                                      C.byref(st)))
         return res, st.as_dict()
+
+    def moments_variance(self, sum, sumsq, n: int = 0, spp=None):
+        """moments_variance() by a kernel on this context's device (pt_ctx_moments_variance), the
+        same bits. numpy arrays go through host pointers; contiguous torch tensors on this
+        context's device (float64 sums, int32 spp) through device pointers, the result is a
+        tensor there. The call first waits for the work queued on torch's current stream of the
+        device (the tensors may come from torch operations still in flight)."""
+        if _is_tensor(sum):
+            import torch
+            for x, dt in ((sum, torch.float64), (sumsq, torch.float64)) + (((spp, torch.int32),) if spp is not None else ()):
+                if not _is_tensor(x) or not x.is_cuda or not x.is_contiguous() or x.dtype != dt:
+                    raise ValueError("sum and sumsq must be contiguous float64 tensors, spp int32, on the context's device")
+            npix = sum.numel() // 3
+            if sum.numel() != 3 * npix or sumsq.numel() != 3 * npix or (spp is not None and spp.numel() != npix):
+                raise ValueError("sum and sumsq must hold pixels x 3 elements, spp one per pixel")
+            var = torch.empty(sum.shape, dtype=torch.float32, device=sum.device)
+            _own_device_tensors(self.device, sum, sumsq, spp)
+            check(lib().pt_ctx_moments_variance(self.h, C.c_void_p(sum.data_ptr()), C.c_void_p(sumsq.data_ptr()), npix, n,
+                                                C.c_void_p(spp.data_ptr()) if spp is not None else None,
+                                                C.c_void_p(var.data_ptr()), 1))
+            return var
+        S, Q, sp, npix = _variance_args(sum, sumsq, spp)
+        var = np.empty(S.shape, dtype=np.float32)
+        check(lib().pt_ctx_moments_variance(self.h, S.ctypes.data, Q.ctypes.data, npix, n,
+                                            sp.ctypes.data if sp is not None else None, var.ctypes.data, 0))
+        return var
+
+    def denoise(self, color, guides, var=None, passes: int = 0, sigma_l: float = 0.0, sigma_z: float = 0.0,
+                normal_pow_log2: int = 0, eps: float = 0.0, out=None, var_out=None):
+        """denoise() on this context's device (pt_ctx_denoise), the same bits: (out, var_out or
+        None, stats). numpy arrays go through host pointers. Contiguous torch tensors on this
+        context's device (float32; guides["tri"] int32) go through device pointers: `out` (and
+        `var_out`, only with var) are written in place and may be `color` (and `var`)
+        themselves; without them new tensors are made (var_out whenever var is given). The
+        library's stream does not order itself after torch's: the call first waits for the work
+        queued on torch's current stream of the device, so guides from denoise_guides() or any
+        other torch operation still in flight are complete when the filter reads them, and it
+        returns after its own work is complete. With numpy arrays `out` and `var_out` must be
+        None (ValueError). stats =
+        {"kernel_ms", "total_ms", "passes", "launches", "form" (per pass "direct" or "lds"),
+        "pass_ms", "pack_ms"}. Needs no scene and leaves a running sum as it is."""
+        prm = _lib.pt_denoise_params(passes, sigma_l, sigma_z, normal_pow_log2, eps)
+        st = _lib.pt_denoise_stats()
+        if _is_tensor(color):
+            import torch
+            if color.dim() != 3 or color.shape[2] != 3:
+                raise ValueError("color must have shape (H, W, 3)")
+            H, W = color.shape[0], color.shape[1]
+            if out is None:
+                out = torch.empty_like(color)
+            if var is not None and var_out is None:
+                var_out = torch.empty_like(color)
+            g = _lib.pt_denoise_guides()
+            tens = [(color, 3, torch.float32), (out, 3, torch.float32)]
+            tens += [(x, 3, torch.float32) for x in (var, var_out) if x is not None]
+            for k in _lib.pt_denoise_guides.NAMES:
+                x = guides[k]
+                tens.append((x, _lib.pt_denoise_guides.WIDTH[k], torch.int32 if k == "tri" else torch.float32))
+                setattr(g, k, x.data_ptr() if _is_tensor(x) else None)
+            for x, w, dt in tens:
+                if not _is_tensor(x) or not x.is_cuda or not x.is_contiguous() or x.dtype != dt or x.numel() != H * W * w:
+                    raise ValueError("color, var, the guides and the outputs must be contiguous float32 (tri: int32) "
+                                     "tensors of H*W*width elements on the context's device")
+            _own_device_tensors(self.device, *[x for x, _, _ in tens])
+            check(lib().pt_ctx_denoise(self.h, W, H, C.c_void_p(color.data_ptr()),
+                                       C.c_void_p(var.data_ptr()) if var is not None else None, C.byref(g), C.byref(prm),
+                                       C.c_void_p(out.data_ptr()),
+                                       C.c_void_p(var_out.data_ptr()) if var_out is not None else None, 1, C.byref(st)))
+            return out, var_out, st.as_dict()
+        if out is not None or var_out is not None:
+            raise ValueError("out and var_out are for torch tensors; numpy results are returned")
+        W, H, c, v, g, _keep = _denoise_args(color, var, guides)
+        res = np.empty((H, W, 3), dtype=np.float32)
+        vres = np.empty((H, W, 3), dtype=np.float32) if v is not None else None
+        check(lib().pt_ctx_denoise(self.h, W, H, c.ctypes.data, v.ctypes.data if v is not None else None, C.byref(g),
+                                   C.byref(prm), res.ctypes.data, vres.ctypes.data if vres is not None else None, 0,
+                                   C.byref(st)))
+        return res, vres, st.as_dict()
+
+    def render_denoised(self, camera: Camera, depth: int, rel: float, abs: float = 0.0, min_samples: int = 16,
+                        max_samples: int = 4096, step: int = 0, max_unconverged: int = 0, sparse_below: float = 0.0,
+                        seed: int = PT_SEED, part_count: int = 1, passes: int = 0, sigma_l: float = 0.0,
+                        sigma_z: float = 0.0, normal_pow_log2: int = 0, eps: float = 0.0, out=None):
+        """render_adaptive + the first-hit guides of sample 0 + the variance of the mean with each
+        pixel's own sample count + denoise, all on the device (pt_ctx_render_denoised): (img,
+        noisy, spp, info). img is bit-identical to making the four calls by hand, noisy and spp
+        are render_adaptive's image and sample counts. info = render_adaptive's, with "denoise"
+        (Renderer.denoise's stats), "aov_ms", "variance_ms" and the whole call's "total_ms". The
+        whole image must be on this device: part_count > 1 raises PTError. `out`: None (numpy
+        results) or a float32 torch tensor of H*W*3 elements on this context's device, written in
+        place (after the work queued on torch's current stream of the device is complete); noisy
+        and spp are then tensors there."""
+        W, H = camera.res
+        prm = _lib.pt_params(0, depth, seed, 0, part_count, 1, 0, 0)
+        ad = _lib.pt_adaptive(_lib.pt_converge(rel, abs, min_samples, max_samples, step, max_unconverged), sparse_below)
+        dp = _lib.pt_denoise_params(passes, sigma_l, sigma_z, normal_pow_log2, eps)
+        rs, ds = _lib.pt_adaptive_stats(), _lib.pt_denoised_stats()
+        if out is None:
+            img = np.empty((H, W, 3), dtype=np.float32)
+            noisy = np.empty((H, W, 3), dtype=np.float32)
+            spp = np.empty((H, W), dtype=np.int32)
+            ptrs, dev = (img.ctypes.data, noisy.ctypes.data, spp.ctypes.data), 0
+        else:
+            import torch
+            if not _is_tensor(out) or not out.is_cuda or out.dtype != torch.float32 or out.numel() != H * W * 3 \
+                    or not out.is_contiguous():
+                raise ValueError("out must be a contiguous float32 tensor with H*W*3 elements on the context's device")
+            img = out
+            noisy = torch.empty((H, W, 3), dtype=torch.float32, device=out.device)
+            spp = torch.empty((H, W), dtype=torch.int32, device=out.device)
+            ptrs, dev = (img.data_ptr(), noisy.data_ptr(), spp.data_ptr()), 1
+            _own_device_tensors(self.device, out)
+        check(lib().pt_ctx_render_denoised(self.h, C.byref(camera.c), C.byref(prm), C.byref(ad), C.byref(dp),
+                                           C.c_void_p(ptrs[0]), C.c_void_p(ptrs[1]), C.c_void_p(ptrs[2]), dev,
+                                           C.byref(rs), C.byref(ds)))
+        info = rs.as_dict()
+        info["render_ms"] = info["total_ms"]
+        info.update(denoise=ds.denoise.as_dict(), aov_ms=ds.aov_ms, variance_ms=ds.variance_ms, total_ms=ds.total_ms)
+        return img, noisy, spp, info
 
 
 def render(camera: Camera, bvh: BVH, samples: int, depth: int, seed: int = PT_SEED, device: int = 0,
@@ -832,6 +976,87 @@ def moments_unconverged(sum, sumsq, n: int, rel: float, abs: float = 0.0, mask: 
     check(lib().pt_moments_unconverged(S.ctypes.data, Q.ctypes.data, npix, n, C.c_float(rel), C.c_float(abs),
                                        C.byref(cnt), m.ctypes.data if mask else None))
     return (cnt.value, m) if mask else cnt.value
+
+
+def _variance_args(sum, sumsq, spp):
+    S = np.ascontiguousarray(sum, dtype=np.float64)
+    Q = np.ascontiguousarray(sumsq, dtype=np.float64)
+    if S.shape != Q.shape or S.size % 3:
+        raise ValueError("sum and sumsq must have the same shape, three channels per pixel")
+    npix = S.size // 3
+    sp = None
+    if spp is not None:
+        sp = np.ascontiguousarray(spp, dtype=np.int32)
+        if sp.size != npix:
+            raise ValueError("spp must hold one count per pixel")
+    return S, Q, sp, npix
+
+
+def moments_variance(sum, sumsq, n: int = 0, spp=None) -> np.ndarray:
+    """The variance of the mean from per-pixel sample moments on the host (pt_moments_variance; no
+    device needed): float32, the shape of `sum`. Per channel, in double: max(0, (Q - S*S/n) /
+    (n - 1)) / n, +inf below two samples. n: one count for the image, or with `spp` (int32, one
+    per pixel: render_adaptive's) each pixel's own. Not sem**2: sem is rounded after its root."""
+    S, Q, sp, npix = _variance_args(sum, sumsq, spp)
+    var = np.empty(S.shape, dtype=np.float32)
+    check(lib().pt_moments_variance(S.ctypes.data, Q.ctypes.data, npix, n, sp.ctypes.data if sp is not None else None,
+                                    var.ctypes.data))
+    return var
+
+
+def denoise_guides(aov: dict) -> dict:
+    """The denoiser's guides from Renderer.aov's channels ("normal", "t", "tri", "emission" and
+    "ray"): those four and "position" = o + d * t in float32, the multiplication rounded before
+    the addition (as trace() forms its hit point). numpy arrays or torch tensors; on tensors the
+    two operations are queued on torch's current stream, which Renderer.denoise waits for."""
+    ray, t = aov["ray"], aov["t"]
+    m = ray[..., 3:6] * t[..., None]
+    pos = ray[..., 0:3] + m
+    pos = pos.contiguous() if _is_tensor(pos) else np.ascontiguousarray(pos, dtype=np.float32)
+    return {"normal": aov["normal"], "t": t, "tri": aov["tri"], "emission": aov["emission"], "position": pos}
+
+
+def _denoise_args(color, var, guides):
+    c = np.ascontiguousarray(color, dtype=np.float32)
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ValueError("color must have shape (H, W, 3)")
+    H, W = c.shape[0], c.shape[1]
+    v = None
+    if var is not None:
+        v = np.ascontiguousarray(var, dtype=np.float32)
+        if v.shape != c.shape:
+            raise ValueError("var must have the shape of color")
+    g, keep = _lib.pt_denoise_guides(), []
+    for k in _lib.pt_denoise_guides.NAMES:
+        a = guides.get(k)
+        if a is None:
+            continue  # the library reports the missing guide
+        a = np.ascontiguousarray(a, dtype=np.int32 if k == "tri" else np.float32)
+        if a.size != H * W * _lib.pt_denoise_guides.WIDTH[k]:
+            raise ValueError(f"guides[{k!r}] must hold H*W*{_lib.pt_denoise_guides.WIDTH[k]} elements")
+        keep.append(a)
+        setattr(g, k, a.ctypes.data)
+    return W, H, c, v, g, keep
+
+
+def denoise(color, guides, var=None, passes: int = 0, sigma_l: float = 0.0, sigma_z: float = 0.0,
+            normal_pow_log2: int = 0, eps: float = 0.0):
+    """The variance-guided a-trous denoiser on the host (pt_image_denoise; no device needed; the
+    definition is in include/pt_hip.h): `passes` (default 5) edge-avoiding B3-spline passes with
+    strides 1, 2, 4, ... over `color` (H, W, 3) float32, rows in render()'s order. A tap counts
+    by the agreement of the first hit's normals (power 2**normal_pow_log2, default 2**7), by the
+    distance of its hit point from the centre's tangent plane (sigma_z, default 0.01, of the hit
+    distance) and, with `var` (the variance of the mean, moments_variance()), by the luminance
+    difference in standard deviations (sigma_l, default 1); misses, emitters and other hits never
+    mix. guides: denoise_guides() of an AOV. Returns (out, var_out): var_out is the filtered
+    variance, None without `var`. A 0 selects a parameter's default."""
+    W, H, c, v, g, _keep = _denoise_args(color, var, guides)
+    prm = _lib.pt_denoise_params(passes, sigma_l, sigma_z, normal_pow_log2, eps)
+    out = np.empty((H, W, 3), dtype=np.float32)
+    vout = np.empty((H, W, 3), dtype=np.float32) if v is not None else None
+    check(lib().pt_image_denoise(W, H, c.ctypes.data, v.ctypes.data if v is not None else None, C.byref(g), C.byref(prm),
+                                 out.ctypes.data, vout.ctypes.data if vout is not None else None))
+    return out, vout
 
 
 def devices_release() -> None:

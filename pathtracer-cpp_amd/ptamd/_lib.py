@@ -34,6 +34,7 @@ EXPORTED = (
     "pt_debug_emit_reject", "pt_debug_emit_box", "pt_debug_ctx_emit_reject", "pt_debug_emit_slab_reject", "pt_debug_ray_stack",
     "pt_ctx_render_moments", "pt_moments_unconverged", "pt_ctx_unconverged", "pt_ctx_render_converge",
     "pt_ctx_render_adaptive",
+    "pt_moments_variance", "pt_ctx_moments_variance", "pt_image_denoise", "pt_ctx_denoise", "pt_ctx_render_denoised",
 )
 PT_MAX_DEVICES = 16
 
@@ -161,6 +162,39 @@ class pt_adaptive_stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class pt_denoise_guides(C.Structure):
+    """The denoiser's first-hit guides (include/pt_hip.h): all five are needed."""
+    NAMES = ("normal", "t", "tri", "emission", "position")
+    WIDTH = {"normal": 3, "t": 1, "tri": 1, "emission": 3, "position": 3}
+    _fields_ = [(k, C.c_void_p) for k in NAMES]
+
+
+class pt_denoise_params(C.Structure):
+    """A 0 selects the default: 5 passes, sigma_l 1, sigma_z 0.01, normal power 2^7, eps 1e-6."""
+    _fields_ = [("passes", C.c_int32), ("sigma_l", C.c_float), ("sigma_z", C.c_float), ("normal_pow_log2", C.c_int32),
+                ("eps", C.c_float)]
+
+
+PT_DENOISE_DIRECT, PT_DENOISE_LDS = 1, 2
+
+
+class pt_denoise_stats(C.Structure):
+    FORMS = {0: None, PT_DENOISE_DIRECT: "direct", PT_DENOISE_LDS: "lds"}
+    _fields_ = [("kernel_ms", C.c_double), ("total_ms", C.c_double), ("passes", C.c_int32), ("launches", C.c_int32),
+                ("form", C.c_int32 * 8), ("pass_ms", C.c_float * 8), ("pack_ms", C.c_float), ("reserved", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        n = self.passes
+        return {"kernel_ms": self.kernel_ms, "total_ms": self.total_ms, "passes": n, "launches": self.launches,
+                "form": [self.FORMS[f] for f in list(self.form)[:n]], "pass_ms": list(self.pass_ms)[:n],
+                "pack_ms": self.pack_ms}
+
+
+class pt_denoised_stats(C.Structure):
+    _fields_ = [("total_ms", C.c_double), ("aov_ms", C.c_double), ("variance_ms", C.c_double),
+                ("denoise", pt_denoise_stats)]
+
+
 class pt_aov(C.Structure):
     """First-hit channels (include/pt_hip.h); a NULL pointer skips the channel."""
     CHANNELS = ("t", "tri", "normal", "albedo", "emission", "ray")
@@ -169,6 +203,7 @@ class pt_aov(C.Structure):
 
 
 assert C.sizeof(pt_bvh_node) == 40 and C.sizeof(pt_material) == 32 and C.sizeof(pt_trace_stats) == 64
+assert C.sizeof(pt_denoise_params) == 20 and C.sizeof(pt_denoise_stats) == 96 and C.sizeof(pt_denoise_guides) == 40
 
 
 class PTError(RuntimeError):
@@ -277,6 +312,16 @@ def lib() -> C.CDLL:
         if hasattr(L, "pt_ctx_render_adaptive"):  # absent from older builds used in A/B runs
             L.pt_ctx_render_adaptive.argtypes = [P, C.POINTER(pt_camera), C.POINTER(pt_params), C.POINTER(pt_adaptive), P,
                                                  C.POINTER(pt_moments), P, C.c_int, C.POINTER(pt_adaptive_stats)]
+        if hasattr(L, "pt_ctx_denoise"):  # absent from older builds used in A/B runs
+            L.pt_moments_variance.argtypes = [P, P, C.c_int64, C.c_int32, P, P]
+            L.pt_ctx_moments_variance.argtypes = [P, P, P, C.c_int64, C.c_int32, P, P, C.c_int]
+            L.pt_image_denoise.argtypes = [C.c_int32, C.c_int32, P, P, C.POINTER(pt_denoise_guides),
+                                           C.POINTER(pt_denoise_params), P, P]
+            L.pt_ctx_denoise.argtypes = [P, C.c_int32, C.c_int32, P, P, C.POINTER(pt_denoise_guides),
+                                         C.POINTER(pt_denoise_params), P, P, C.c_int, C.POINTER(pt_denoise_stats)]
+            L.pt_ctx_render_denoised.argtypes = [P, C.POINTER(pt_camera), C.POINTER(pt_params), C.POINTER(pt_adaptive),
+                                                 C.POINTER(pt_denoise_params), P, P, P, C.c_int,
+                                                 C.POINTER(pt_adaptive_stats), C.POINTER(pt_denoised_stats)]
         if hasattr(L, "pt_debug_rccl_failover"):  # test hooks (absent from older builds used in A/B runs)
             L.pt_debug_rccl_failover.argtypes = [C.c_int32, C.c_int32, P]
         if hasattr(L, "pt_debug_rtc_cache"):
