@@ -17,6 +17,8 @@
  *   pt_ctx_render_moments / pt_ctx_unconverged / pt_ctx_render_converge: the render's per-pixel
  *                                       sample moments, their error estimate, rendering to a noise target
  *   pt_ctx_render_adaptive: the same with the later rounds only for the pixels that miss the target
+ *   pt_image_temporal / pt_ctx_temporal / pt_ctx_render_temporal <- render_realtime()'s moving camera,
+ *                                       render.h:219-387: frames accumulated across camera moves by reprojection
  *   pt_bvh_build                     <- BVH::build()  bvh.h:79-155 (find_best_axis 48-78)
  *   pt_camera_init                   <- Camera::Camera() camera.h:33-61
  *   pt_sample_seed                   <- rng.h:32 global LCG (stream policy, see below)
@@ -559,6 +561,145 @@ typedef struct pt_denoised_stats {
 int pt_ctx_render_denoised(pt_ctx* ctx, const pt_camera* cam, const pt_params* params, const pt_adaptive* adaptive,
                            const pt_denoise_params* denoise_params, float* out, float* noisy_out, int32_t* spp_out,
                            int out_is_device, pt_adaptive_stats* render_stats, pt_denoised_stats* stats);
+
+/* ---- temporal reprojection: accumulating frames across camera moves ----------------
+ * The temporal part of SVGF for a static scene and a moving camera (render_realtime's use,
+ * render.h:219-387): every pixel's first hit is projected into the previous frame's camera, the
+ * previous frame's accumulated colour is gathered there where the surfaces agree, and the two are
+ * blended. The result and its variance are what the a-trous filter above takes. Defined bit for
+ * bit: float32 throughout, only + - * /, floorf, fabsf and comparisons, each rounded on its own (no
+ * fused multiply-add), every dot product ((a.x*b.x) + (a.y*b.y)) + (a.z*b.z); the host form and the
+ * device form return the same bits.
+ *
+ * Planes. All are W x H, rows in pt_ctx_render's order. A history (pt_temporal_history) is seven
+ * planes: color, m2 (the accumulated second moment of the frames' means), var: 3 floats each;
+ * hist: 1 int32, the frames accumulated (>= 1 once written; < 1 marks a hole that is never read);
+ * normal, position: 3 floats, cls: 1 int32, the guides of the frame that wrote it. cls is the
+ * denoiser's class: 0 for a miss (tri < 0), 2 for a hit with any emission channel != 0, else 1.
+ * A call reads the history `prev` (NULL: the first frame, every pixel is without history) and
+ * writes every plane of `next`. Every pointer of `next` is required; of `prev`, every one but
+ * `var`, which is read in sample mode only. It is a gather: a plane of `prev` that overlaps a
+ * plane of `next` in memory is PT_E_ARG. `next` may alias the current frame's inputs (a pixel
+ * reads its own inputs before it writes).
+ *
+ * Inputs. cam_cur and cam_prev (required with prev; only pos, v_res, cell_size, distance and
+ * transform are read, not res), the current frame's color c (3 floats per pixel), its variance v
+ * as a mean (optional, pt_moments_variance), the denoiser's five guides of the current frame
+ * (pt_denoise_guides, all required) and pt_temporal_params.
+ *
+ * proj(cam, X), the inverse of Camera::get_ray (camera.h:63-73) without its jitter:
+ *     d = X - cam.pos per component;  cx, cy, cz = d . row 0, 1, 2 of cam.transform;
+ *     valid only if cz < 0 (false for a NaN);  k = (0.0f - cam.distance) / cz;
+ *     fx = ((cx*k) + (0.5f*cam.v_res[0])) / cam.cell_size;  fy = ((cy*k) + (0.5f*cam.v_res[1])) / cam.cell_size.
+ *
+ * Per pixel p = (w, h), with n_p, X_p, t_p, cls_p the current guides:
+ *  1. cls_p == 0: no history (a miss carries no hit point).
+ *  2. (fxc, fyc) = proj(cam_cur, X_p), (fxp, fyp) = proj(cam_prev, X_p); either invalid: no history.
+ *     gx = (float)w + (fxp - fxc); gy = (float)h + (fyp - fyc). This is the motion-vector form: the
+ *     AOV's hit point is jittered inside its pixel, and the projection into the current camera
+ *     takes that offset out again.
+ *  3. Unless gx > -1 && gx < (float)W && gy > -1 && gy < (float)H: no history (a NaN fails).
+ *     x0 = (int)floorf(gx); ax = gx - (float)x0; y0 and ay likewise.
+ *  4. Taps: j = 0, 1 outer, k = 0, 1 inner, q = (x0 + k, y0 + j); a tap outside the image is
+ *     skipped. wx = [1.0f - ax, ax], wy likewise, bw = wx_k * wy_j. A tap counts only if, tested in
+ *     this order, bw > 0; hist_prev(q) >= 1; cls_prev(q) == cls_p; n_p . n_prev(q) > normal_min;
+ *     |n_p . (X_prev(q) - X_p)| < sigma_z * t_p (the difference per component first); and every
+ *     channel of color_prev(q) has fabsf(c) < +inf. For a counting tap: Wsum += bw; per channel
+ *     A += bw*color_prev(q), M += bw*m2_prev(q) and, in sample mode, V += bw*var_prev(q) (all from
+ *     +0); Nmin = min(Nmin, hist_prev(q)).
+ *  5. Unless Wsum > 0: no history. Otherwise the pixel reuses its history: per channel pc = A/Wsum,
+ *     pm = M/Wsum, pv = V/Wsum; N' = min(Nmin, max_history - 1) + 1; alpha = 1.0f/(float)N';
+ *     b = 1.0f - alpha;
+ *         c'  = (b*pc) + (alpha*c);      m2' = (b*pm) + (alpha*(c*c));
+ *         sample mode:   v' = ((b*b)*pv) + ((alpha*alpha)*v)  (independent estimates: the variances
+ *                        add with squared weights);
+ *         temporal mode: d = m2' - (c'*c'); d = d > 0 ? d : 0; v' = d*alpha.
+ *  6. No history: c' = c, m2' = c*c, N' = 1; v' = v in sample mode, +inf in temporal mode
+ *     (pt_moments_variance's convention below two samples: the filter then lets the guides decide).
+ *  7. next receives c', m2', v', N' and the current frame's normal, position and cls.
+ * `reused` is the number of pixels that took step 5.
+ *
+ * Consequences. With cam_prev equal to cam_cur bit for bit the two projections are the same bits,
+ * their difference is exactly 0 and the lookup is exactly pixel p with weight 1: a static camera
+ * never blurs its history, and c' follows c_N = (b*c_{N-1}) + (alpha*c) with alpha = 1/N until N
+ * reaches max_history, where it stays. A NaN or infinite current colour goes into c' of its own
+ * pixel only: the next frame's taps drop it (the test on color_prev), so it lasts one frame and
+ * the pixel starts again. m2_prev and var_prev are not tested; a history written by this function
+ * from finite frames holds none. A camera that looks away from a hit point (cz >= 0, in either
+ * camera) gives no history, as does a projection that overflows (inf - inf is a NaN). The planes
+ * of prev are W x H of this call: after a change of resolution the caller passes prev = NULL. var
+ * is interpolated linearly, not with squared weights, on purpose: neighbouring histories share
+ * most of their samples after a move, so they are correlated and squared weights would promise
+ * too much. hist above max_history (a history written with a larger one) is clamped by step 5. */
+typedef struct pt_temporal_history {
+    float* color;                /* 3 floats per pixel: the accumulated, unfiltered colour */
+    float* m2;                   /* 3 floats: the accumulated c*c */
+    float* var;                  /* 3 floats: v' */
+    int32_t* hist;               /* 1 int32: N' */
+    float* normal;               /* 3 floats */
+    float* position;             /* 3 floats */
+    int32_t* cls;                /* 1 int32: 0, 1 or 2 */
+} pt_temporal_history;
+
+#define PT_TEMPORAL_VAR_SAMPLE 1   /* v' from the frames' own variances; needs var and, with prev, prev->var */
+#define PT_TEMPORAL_VAR_TEMPORAL 2 /* v' from the accumulated moments; var is ignored */
+/* A 0 selects the default; max_history outside 0..65535, a negative or NaN float, normal_min >= 1
+ * or another variance_mode is PT_E_ARG. A NULL pt_temporal_params selects every default. */
+typedef struct pt_temporal_params {  /* 16 bytes */
+    int32_t max_history;         /* 0 (default: 32) or 1..65535 */
+    float sigma_z;               /* > 0, default 0.01: plane-distance tolerance as a fraction of t_p */
+    float normal_min;            /* in (0, 1), default 0.9 */
+    int32_t variance_mode;       /* 0 (default: sample mode with var, else temporal mode) or PT_TEMPORAL_VAR_* */
+} pt_temporal_params;
+
+typedef struct pt_temporal_stats {   /* 24 bytes */
+    double kernel_ms;            /* the kernel's duration (HIP events) */
+    double total_ms;             /* end-to-end wall time of the call   */
+    int64_t reused;              /* pixels that reused their history   */
+} pt_temporal_stats;
+
+/* One frame's accumulation on the host (no device needed). W, H >= 1, W*H <= 2^30. reused is optional. */
+int pt_image_temporal(int32_t W, int32_t H, const pt_camera* cam_cur, const pt_camera* cam_prev, const float* color,
+                      const float* var, const pt_denoise_guides* guides, const pt_temporal_history* prev,
+                      const pt_temporal_history* next, const pt_temporal_params* params, int64_t* reused);
+/* The same on the context's device, bit-identical, `reused` (counted by ballot, one atomic per
+ * wave) included. is_device != 0: color, var, the guides and every plane of prev and next are
+ * device pointers on the context's device. Needs no scene, is synchronous and leaves a running sum
+ * as it is. stats is optional. */
+int pt_ctx_temporal(pt_ctx* ctx, int32_t W, int32_t H, const pt_camera* cam_cur, const pt_camera* cam_prev,
+                    const float* color, const float* var, const pt_denoise_guides* guides,
+                    const pt_temporal_history* prev, const pt_temporal_history* next,
+                    const pt_temporal_params* params, int is_device, pt_temporal_stats* stats);
+
+typedef struct pt_render_temporal_stats {
+    double total_ms;             /* end-to-end wall time of the call */
+    double render_ms;            /* pt_ctx_render_moments' total_ms */
+    double aov_ms, variance_ms;  /* the AOV kernel's and the position + variance kernels' durations */
+    uint64_t rays;               /* the render's traced segments */
+    int32_t had_history;         /* 1: the frame was accumulated onto the context's history, 0: it started one */
+    int32_t variance_mode;       /* PT_TEMPORAL_VAR_SAMPLE (spp >= 2) or PT_TEMPORAL_VAR_TEMPORAL (spp == 1) */
+    pt_temporal_stats temporal;
+    pt_denoise_stats denoise;
+} pt_render_temporal_stats;
+/* One frame of a camera path without a host round trip between the steps:
+ *   pt_ctx_render_moments of params->spp samples from s_first = 0 at params->seed;
+ *   pt_ctx_render_aov of sample 0 at params->seed; position = o + d * t;
+ *   with spp >= 2 pt_ctx_moments_variance (n = spp) and sample mode, with spp == 1 no var and temporal mode
+ *     (temporal_params->variance_mode must be 0 or that mode, else PT_E_ARG);
+ *   pt_ctx_temporal against the history and the camera the context kept from its last such call;
+ *   pt_ctx_denoise of (c', v') into out.
+ * The caller changes params->seed from frame to frame: frames of one seed repeat their noise and
+ * accumulate nothing. The context owns two histories and alternates between them; the unfiltered
+ * c' is what is kept (and what accumulated_out, optional, W*H*3, receives), never the filtered
+ * image. The history is dropped (the next frame starts one) by reset != 0 (before this frame), by
+ * pt_ctx_set_scene, by a resolution other than the kept one and by any error return of this call,
+ * PT_E_RUNAWAY included (out is still written then). Needs params->part_count <= 1 (else PT_E_ARG).
+ * out (W*H*3) is bit-identical to making the calls by hand; out_is_device covers out and
+ * accumulated_out. Ends a running sum, as any render does. */
+int pt_ctx_render_temporal(pt_ctx* ctx, const pt_camera* cam, const pt_params* params,
+                           const pt_temporal_params* temporal_params, const pt_denoise_params* denoise_params,
+                           int reset, float* out, float* accumulated_out, int out_is_device,
+                           pt_render_temporal_stats* stats);
 
 /* ---- radiance along caller-supplied rays (trace(), render.h:36-61) ------------
  * rgb_out[3 i ..] = (sum over s of trace(bvh, o_i, d_i, depth)) / (float)spp: the sum runs in

@@ -207,6 +207,13 @@ static_assert(dn_tile_bytes(true) <= 65536, "the tiled form's LDS stays within t
 
 }  // namespace
 
+int dn_position_launch(void* stream, const float* ray, const float* t, size_t npix, float* pos) {
+    hipLaunchKernelGGL(pt_dn_position_kernel, dim3(dn_blocks(npix)), dim3(kDnBlock), 0, (hipStream_t)stream, ray, t, npix,
+                       pos);
+    DN_HIP(hipGetLastError());
+    return PT_OK;
+}
+
 }  // namespace pt
 
 using namespace pt;

@@ -27,6 +27,7 @@
 #include "pt_internal.h"
 #include "pt_math.h"
 #include "pt_denoise.h"
+#include "pt_temporal.h"
 #include "pt_moments.h"
 
 namespace pt {
@@ -1033,6 +1034,48 @@ int pt::denoise_check(const char* who, int32_t W, int32_t H, const float* color,
     return PT_OK;
 }
 
+// pt_temporal_params with the defaults filled in and the arguments every form of the temporal
+// reprojection checks (include/pt_hip.h). `who`: the entry point's name for the message.
+int pt::temporal_check(const char* who, int32_t W, int32_t H, const pt_camera* cam_cur, const pt_camera* cam_prev,
+                       const float* color, const float* var, const pt_denoise_guides* g, const pt_temporal_history* prev,
+                       const pt_temporal_history* next, const pt_temporal_params* prm, TpParams* P) {
+    if (W <= 0 || H <= 0 || (int64_t)W * H > (1ll << 30))
+        return set_error(PT_E_ARG, "%s: image of %d x %d pixels", who, W, H);
+    if (!cam_cur || !color || !g || !next || (prev && !cam_prev)) return set_error(PT_E_ARG, "%s: NULL argument", who);
+    if (!g->normal || !g->t || !g->tri || !g->emission || !g->position)
+        return set_error(PT_E_ARG, "%s: normal, t, tri, emission and position are all needed", who);
+    const pt_temporal_params d = prm ? *prm : pt_temporal_params{0, 0.0f, 0.0f, 0};
+    if (d.max_history < 0 || d.max_history > 65535)
+        return set_error(PT_E_ARG, "%s: max_history %d is not 0 (the default) or 1..65535", who, d.max_history);
+    if (!(d.sigma_z >= 0.0f) || !(d.normal_min >= 0.0f) || !(d.normal_min < 1.0f))
+        return set_error(PT_E_ARG, "%s: sigma_z must be positive and normal_min in (0, 1) (0: the default)", who);
+    if (d.variance_mode != 0 && d.variance_mode != PT_TEMPORAL_VAR_SAMPLE && d.variance_mode != PT_TEMPORAL_VAR_TEMPORAL)
+        return set_error(PT_E_ARG, "%s: variance_mode %d", who, d.variance_mode);
+    P->max_history = d.max_history ? d.max_history : 32;
+    P->sigma_z = d.sigma_z != 0.0f ? d.sigma_z : 0.01f;
+    P->normal_min = d.normal_min != 0.0f ? d.normal_min : 0.9f;
+    P->sample = d.variance_mode ? d.variance_mode == PT_TEMPORAL_VAR_SAMPLE : var != nullptr;
+    if (P->sample && (!var || (prev && !prev->var)))
+        return set_error(PT_E_ARG, "%s: sample mode needs var and the previous history's var", who);
+    if (!next->color || !next->m2 || !next->var || !next->hist || !next->normal || !next->position || !next->cls)
+        return set_error(PT_E_ARG, "%s: every plane of the next history is needed", who);
+    if (prev) {
+        if (!prev->color || !prev->m2 || !prev->hist || !prev->normal || !prev->position || !prev->cls)
+            return set_error(PT_E_ARG, "%s: every plane of the previous history but var is needed", who);
+        // the call is a gather: no plane of prev may overlap a plane of next
+        const size_t n = (size_t)W * H;
+        const struct { const void* p; size_t bytes; } a[7] = {{prev->color, 12 * n}, {prev->m2, 12 * n}, {prev->var, 12 * n}, {prev->hist, 4 * n}, {prev->normal, 12 * n}, {prev->position, 12 * n}, {prev->cls, 4 * n}},
+          b[7] = {{next->color, 12 * n}, {next->m2, 12 * n}, {next->var, 12 * n}, {next->hist, 4 * n}, {next->normal, 12 * n}, {next->position, 12 * n}, {next->cls, 4 * n}};
+        for (const auto& x : a)
+            for (const auto& y : b) {
+                const uintptr_t xs = (uintptr_t)x.p, ys = (uintptr_t)y.p;
+                if (x.p && xs < ys + y.bytes && ys < xs + x.bytes)
+                    return set_error(PT_E_ARG, "%s: the previous and the next history overlap", who);
+            }
+    }
+    return PT_OK;
+}
+
 extern "C" {
 
 int pt_abi_version(void) { return PT_ABI_VERSION; }
@@ -1857,6 +1900,26 @@ int pt_image_denoise(int32_t W, int32_t H, const float* color, const float* var,
             var_out[3 * i + 2] = vr[last][i].z;
         }
     }
+    return PT_OK;
+}
+
+// The temporal reprojection on the host: the kernel's loop over tp_pixel (pt_temporal.h).
+int pt_image_temporal(int32_t W, int32_t H, const pt_camera* cam_cur, const pt_camera* cam_prev, const float* color,
+                      const float* var, const pt_denoise_guides* g, const pt_temporal_history* prev,
+                      const pt_temporal_history* next, const pt_temporal_params* prm, int64_t* reused) {
+    TpParams P;
+    if (int rc = temporal_check("pt_image_temporal", W, H, cam_cur, cam_prev, color, var, g, prev, next, prm, &P)) return rc;
+    const TpCam cur = tp_camera(*cam_cur), old = tp_camera(prev ? *cam_prev : *cam_cur);
+    const TpFrame F{color, P.sample ? var : nullptr, g->normal, g->t, g->tri, g->emission, g->position};
+    const TpHist nx{next->color, next->m2, next->var, next->hist, next->normal, next->position, next->cls};
+    TpHist pv{};
+    if (prev) pv = TpHist{prev->color, prev->m2, prev->var, prev->hist, prev->normal, prev->position, prev->cls};
+    int64_t count = 0;
+    for (int y = 0; y < H; y++)
+        for (int x = 0; x < W; x++)
+            count += P.sample ? tp_pixel<true>(W, H, x, y, cur, old, F, pv, prev != nullptr, nx, P)
+                              : tp_pixel<false>(W, H, x, y, cur, old, F, pv, prev != nullptr, nx, P);
+    if (reused) *reused = count;
     return PT_OK;
 }
 

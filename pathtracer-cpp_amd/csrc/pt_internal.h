@@ -221,7 +221,26 @@ int denoise_check(const char* who, int32_t W, int32_t H, const float* color, con
 // (pt_kernel.hip): buffer `slot` (0 records and ping-pong, 1 a host-pointer call's staging,
 // 2 pt_ctx_render_denoised's images and guides) grown to `bytes`. Waits for the context's stream
 // to exist and selects its device.
-constexpr int kDnScratchSlots = 3;
+// Slots 3..6 are the temporal reprojection's (pt_temporal.hip): 3 its counter and a host-pointer
+// call's staging, 4 and 5 the context's two histories, 6 pt_ctx_render_temporal's frame.
+constexpr int kDnScratchSlots = 7;
 int ctx_scratch(pt_ctx* c, int slot, size_t bytes, void** out);
+// position = o + d * t per component of an AOV's rays (6 floats per pixel) on `stream`; no synchronisation.
+int dn_position_launch(void* stream, const float* ray, const float* t, size_t npix, float* pos);
+
+// ---- temporal reprojection (pt_temporal.h, pt_temporal.hip; the host form is in pt_host.cpp) ----
+struct TpParams;
+// The arguments every form checks, and pt_temporal_params with its defaults filled in (pt_host.cpp).
+int temporal_check(const char* who, int32_t W, int32_t H, const pt_camera* cam_cur, const pt_camera* cam_prev,
+                   const float* color, const float* var, const pt_denoise_guides* g, const pt_temporal_history* prev,
+                   const pt_temporal_history* next, const pt_temporal_params* prm, TpParams* P);
+// What a context keeps between two pt_ctx_render_temporal calls (pt_kernel.hip owns it and ends it
+// in pt_ctx_set_scene): the history in scratch slot 4 + `slot` was written for camera `cam`.
+struct TemporalState {
+    bool valid = false;
+    int slot = 0;
+    pt_camera cam{};
+};
+TemporalState* ctx_temporal_state(pt_ctx* c);
 
 }  // namespace pt

@@ -409,6 +409,7 @@ struct pt_ctx {
     // the denoiser's scratch (pt_denoise.hip through ctx_scratch)
     void* d_dn[kDnScratchSlots] = {};
     size_t dn_bytes[kDnScratchSlots] = {};
+    TemporalState temporal;                  // pt_ctx_render_temporal's history (pt_temporal.hip)
     // progressive rendering: d_accum holds the running sum of prog_spp samples; prog_moments: the
     // sum is a moments sum (d_mom continues with it, over prog_npix pixels)
     bool prog_valid = false;
@@ -1451,6 +1452,7 @@ int pt_ctx_set_scene(pt_ctx* c, const pt_scene* scene) {
     c->d_rank_tri = nullptr;
     c->have_scene = false;
     c->prog_valid = false;
+    c->temporal.valid = false;
     HIP_TRY(hipMalloc((void**)&c->d_nodes, ps.nodes.size() * sizeof(float4)));
     HIP_TRY(hipMalloc((void**)&c->d_tris, ps.tris.size() * sizeof(float4)));
     HIP_TRY(hipMalloc((void**)&c->d_mats, ps.mats.size() * sizeof(float4)));
@@ -2375,6 +2377,8 @@ int pt::ctx_scratch(pt_ctx* c, int slot, size_t bytes, void** out) {
 }
 
 void* pt::ctx_stream(pt_ctx* c) { return c && ctx_ready(c) == PT_OK ? (void*)c->stream : nullptr; }
+
+pt::TemporalState* pt::ctx_temporal_state(pt_ctx* c) { return &c->temporal; }
 
 // Quantise a device image of `rows` x W pixels into d_dst (synchronous).
 int pt::rgb8_device(pt_ctx* c, const float* d_lin, int rows, int W, float gamma, int flip, uint8_t* d_dst) {

@@ -29,6 +29,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
+from ._lib import PT_TEMPORAL_VAR_SAMPLE, PT_TEMPORAL_VAR_TEMPORAL  # noqa: F401
 from ._lib import PT_MAX_DEPTH, PT_SEED, PTError, build, check, lib  # noqa: F401
 from . import scenes  # noqa: F401
 
@@ -904,6 +905,106 @@ class Renderer:
         info.update(denoise=ds.denoise.as_dict(), aov_ms=ds.aov_ms, variance_ms=ds.variance_ms, total_ms=ds.total_ms)
         return img, noisy, spp, info
 
+    def temporal_accumulate(self, color, guides, camera: Camera, prev: Optional["TemporalHistory"] = None,
+                            prev_camera: Optional[Camera] = None, var=None, max_history: int = 0, sigma_z: float = 0.0,
+                            normal_min: float = 0.0, variance_mode: int = 0, out: Optional["TemporalHistory"] = None):
+        """temporal_accumulate() on this context's device (pt_ctx_temporal), the same bits:
+        (next, stats) with stats = {"kernel_ms", "total_ms", "reused"}. numpy arrays go through
+        host pointers (`out` must then be None). Contiguous torch tensors on this context's device
+        (float32; guides["tri"], hist and cls int32) go through device pointers: color, var, every
+        guide and every plane of `prev` must then be such tensors (ValueError otherwise), `next` is
+        `out` or a new TemporalHistory of tensors, and must not share memory with `prev`
+        (PTError). The validation and the wait for torch's current stream are Renderer.denoise's.
+        The inputs are left untouched. Needs no scene and leaves a running sum as it is."""
+        prm = _lib.pt_temporal_params(max_history, sigma_z, normal_min, variance_mode)
+        st = _lib.pt_temporal_stats()
+        if prev is not None and prev_camera is None:
+            raise ValueError("prev needs prev_camera")
+        pc = C.byref(prev_camera.c) if prev is not None else None
+        if _is_tensor(color):
+            import torch
+            if color.dim() != 3 or color.shape[2] != 3:
+                raise ValueError("color must have shape (H, W, 3)")
+            H, W = color.shape[0], color.shape[1]
+            if out is None:
+                out = TemporalHistory.empty(W, H, like=color)
+            tens = [(color, 3, torch.float32)] + ([(var, 3, torch.float32)] if var is not None else [])
+            g = _lib.pt_denoise_guides()
+            for k in _lib.pt_denoise_guides.NAMES:
+                x = guides[k]
+                tens.append((x, _lib.pt_denoise_guides.WIDTH[k], torch.int32 if k == "tri" else torch.float32))
+                setattr(g, k, x.data_ptr() if _is_tensor(x) else None)
+            hs = []
+            for h in (prev, out):
+                s = _lib.pt_temporal_history()
+                for k in _lib.pt_temporal_history.NAMES if h is not None else ():
+                    x = getattr(h, k)
+                    if x is None and h is prev and k == "var":
+                        continue  # the library reports it when sample mode needs it
+                    tens.append((x, _lib.pt_temporal_history.WIDTH[k],
+                                 torch.int32 if k in _lib.pt_temporal_history.INT else torch.float32))
+                    setattr(s, k, x.data_ptr() if _is_tensor(x) else None)
+                hs.append(s)
+            for x, w, dt in tens:
+                if not _is_tensor(x) or not x.is_cuda or not x.is_contiguous() or x.dtype != dt or x.numel() != H * W * w:
+                    raise ValueError("color, var, the guides and the histories' planes must be contiguous float32 "
+                                     "(tri, hist, cls: int32) tensors of H*W*width elements on the context's device")
+            _own_device_tensors(self.device, *[x for x, _, _ in tens])
+            check(lib().pt_ctx_temporal(self.h, W, H, C.byref(camera.c), pc, C.c_void_p(color.data_ptr()),
+                                        C.c_void_p(var.data_ptr()) if var is not None else None, C.byref(g),
+                                        C.byref(hs[0]) if prev is not None else None, C.byref(hs[1]), C.byref(prm), 1,
+                                        C.byref(st)))
+            return out, st.as_dict()
+        if out is not None:
+            raise ValueError("out is for torch tensors; numpy results are returned")
+        _no_tensors(color, var, guides)
+        W, H, c, v, g, _keep = _denoise_args(color, var, guides)
+        ps, _pkeep = _history_host(prev, W, H) if prev is not None else (None, None)
+        nxt = TemporalHistory.empty(W, H)
+        ns, _nkeep = _history_host(nxt, W, H)
+        check(lib().pt_ctx_temporal(self.h, W, H, C.byref(camera.c), pc, c.ctypes.data,
+                                    v.ctypes.data if v is not None else None, C.byref(g),
+                                    C.byref(ps) if ps is not None else None, C.byref(ns), C.byref(prm), 0, C.byref(st)))
+        return nxt, st.as_dict()
+
+    def render_temporal(self, camera: Camera, spp: int, depth: int, seed: int = PT_SEED, reset: bool = False,
+                        max_history: int = 0, temporal_sigma_z: float = 0.0, normal_min: float = 0.0, passes: int = 0,
+                        sigma_l: float = 0.0, sigma_z: float = 0.0, normal_pow_log2: int = 0, eps: float = 0.0,
+                        part_count: int = 1, out=None):
+        """One frame of a camera path, all on the device (pt_ctx_render_temporal): render_moments
+        of `spp` samples + the first-hit guides of sample 0 + the variance of the mean (spp >= 2;
+        with spp = 1 the accumulated moments give it) + temporal_accumulate onto the history this
+        context kept from its last render_temporal + denoise. Returns (img, accumulated, info):
+        img is bit-identical to making the calls by hand, accumulated is the unfiltered
+        accumulation (what the context keeps as history). Change `seed` from frame to frame.
+        The history is dropped by reset=True, set_scene, another resolution or an error.
+        info = {"total_ms", "render_ms", "aov_ms", "variance_ms", "rays", "had_history",
+        "variance_mode", "reused", "temporal", "denoise"}. part_count > 1 raises PTError. `out`:
+        None (numpy results) or a float32 torch tensor of H*W*3 elements on this context's device,
+        written in place (after the work queued on torch's current stream of the device is
+        complete); accumulated is then a tensor there."""
+        W, H = camera.res
+        prm = _lib.pt_params(spp, depth, seed, 0, part_count, 1, 0, 0)
+        tp = _lib.pt_temporal_params(max_history, temporal_sigma_z, normal_min, 0)
+        dp = _lib.pt_denoise_params(passes, sigma_l, sigma_z, normal_pow_log2, eps)
+        st = _lib.pt_render_temporal_stats()
+        if out is None:
+            img = np.empty((H, W, 3), dtype=np.float32)
+            acc = np.empty((H, W, 3), dtype=np.float32)
+            ptrs, dev = (img.ctypes.data, acc.ctypes.data), 0
+        else:
+            import torch
+            if not _is_tensor(out) or not out.is_cuda or out.dtype != torch.float32 or out.numel() != H * W * 3 \
+                    or not out.is_contiguous():
+                raise ValueError("out must be a contiguous float32 tensor with H*W*3 elements on the context's device")
+            img = out
+            acc = torch.empty((H, W, 3), dtype=torch.float32, device=out.device)
+            ptrs, dev = (img.data_ptr(), acc.data_ptr()), 1
+            _own_device_tensors(self.device, out)
+        check(lib().pt_ctx_render_temporal(self.h, C.byref(camera.c), C.byref(prm), C.byref(tp), C.byref(dp), int(bool(reset)),
+                                           C.c_void_p(ptrs[0]), C.c_void_p(ptrs[1]), dev, C.byref(st)))
+        return img, acc, st.as_dict()
+
 
 def render(camera: Camera, bvh: BVH, samples: int, depth: int, seed: int = PT_SEED, device: int = 0,
            devices: Optional[Sequence[int]] = None, band_rows: int = 1, **kw):
@@ -1057,6 +1158,86 @@ def denoise(color, guides, var=None, passes: int = 0, sigma_l: float = 0.0, sigm
     check(lib().pt_image_denoise(W, H, c.ctypes.data, v.ctypes.data if v is not None else None, C.byref(g), C.byref(prm),
                                  out.ctypes.data, vout.ctypes.data if vout is not None else None))
     return out, vout
+
+
+class TemporalHistory:
+    """The seven planes of an accumulated history (pt_temporal_history, include/pt_hip.h), numpy
+    arrays or torch tensors, rows in render()'s order: color, m2, var, normal, position (H, W, 3)
+    float32; hist (frames accumulated, < 1 marks a hole) and cls (H, W) int32."""
+    NAMES = _lib.pt_temporal_history.NAMES
+
+    def __init__(self, color, m2, var, hist, normal, position, cls):
+        self.color, self.m2, self.var, self.hist = color, m2, var, hist
+        self.normal, self.position, self.cls = normal, position, cls
+
+    @classmethod
+    def empty(cls, W: int, H: int, like=None) -> "TemporalHistory":
+        """A history of holes (every plane 0, so hist marks nothing as written): numpy arrays, or
+        with `like` a torch tensor, tensors on its device."""
+        planes = {}
+        for k in cls.NAMES:
+            w = _lib.pt_temporal_history.WIDTH[k]
+            shape = (H, W) if w == 1 else (H, W, w)
+            integer = k in _lib.pt_temporal_history.INT
+            if _is_tensor(like):
+                import torch
+                planes[k] = torch.zeros(shape, dtype=torch.int32 if integer else torch.float32, device=like.device)
+            else:
+                planes[k] = np.zeros(shape, dtype=np.int32 if integer else np.float32)
+        return cls(**planes)
+
+    def planes(self) -> dict:
+        return {k: getattr(self, k) for k in self.NAMES}
+
+
+def _history_host(h: TemporalHistory, W: int, H: int):
+    """pt_temporal_history over a numpy history's own arrays (no copies: `next` is written in place)."""
+    s, keep = _lib.pt_temporal_history(), []
+    for k in _lib.pt_temporal_history.NAMES:
+        a = getattr(h, k)
+        if a is None:
+            continue  # the library reports a missing plane
+        dt = np.int32 if k in _lib.pt_temporal_history.INT else np.float32
+        if _is_tensor(a) or not isinstance(a, np.ndarray) or a.dtype != dt or not a.flags.c_contiguous \
+                or a.size != H * W * _lib.pt_temporal_history.WIDTH[k]:
+            raise ValueError(f"history plane {k!r} must be a contiguous {np.dtype(dt).name} numpy array of "
+                             f"H*W*{_lib.pt_temporal_history.WIDTH[k]} elements")
+        keep.append(a)
+        setattr(s, k, a.ctypes.data)
+    return s, keep
+
+
+def _no_tensors(color, var, guides) -> None:
+    if any(_is_tensor(x) for x in (color, var) + tuple(guides.values())):
+        raise ValueError("numpy arrays and torch tensors cannot be mixed in one call")
+
+
+def temporal_accumulate(color, guides, camera: Camera, prev: Optional[TemporalHistory] = None,
+                        prev_camera: Optional[Camera] = None, var=None, max_history: int = 0, sigma_z: float = 0.0,
+                        normal_min: float = 0.0, variance_mode: int = 0):
+    """One frame of temporal reprojection on the host (pt_image_temporal; no device needed; the
+    definition is in include/pt_hip.h): every pixel's first hit (guides: denoise_guides() of the
+    frame's AOV) is projected into `prev_camera`, the history `prev` is gathered there
+    bilinearly where class, normal (normal_min, default 0.9) and tangent-plane distance (sigma_z,
+    default 0.01, of the hit distance) agree, and blended with `color` (H, W, 3) with weight
+    1/N, N <= max_history (default 32). `var`: the variance of `color` as a mean
+    (moments_variance()); with it (variance_mode 0 or PT_TEMPORAL_VAR_SAMPLE) the variances are
+    combined, without it (or PT_TEMPORAL_VAR_TEMPORAL) the accumulated moments give the variance.
+    prev = None starts a history. Returns (next, reused): a new TemporalHistory whose color and
+    var are what denoise() takes, and the number of pixels that reused their history."""
+    _no_tensors(color, var, guides)
+    W, H, c, v, g, _keep = _denoise_args(color, var, guides)
+    if prev is not None and prev_camera is None:
+        raise ValueError("prev needs prev_camera")
+    ps, _pkeep = _history_host(prev, W, H) if prev is not None else (None, None)
+    nxt = TemporalHistory.empty(W, H)
+    ns, _nkeep = _history_host(nxt, W, H)
+    prm = _lib.pt_temporal_params(max_history, sigma_z, normal_min, variance_mode)
+    reused = C.c_int64(0)
+    check(lib().pt_image_temporal(W, H, C.byref(camera.c), C.byref(prev_camera.c) if prev is not None else None,
+                                  c.ctypes.data, v.ctypes.data if v is not None else None, C.byref(g),
+                                  C.byref(ps) if ps is not None else None, C.byref(ns), C.byref(prm), C.byref(reused)))
+    return nxt, reused.value
 
 
 def devices_release() -> None:

@@ -35,6 +35,7 @@ EXPORTED = (
     "pt_ctx_render_moments", "pt_moments_unconverged", "pt_ctx_unconverged", "pt_ctx_render_converge",
     "pt_ctx_render_adaptive",
     "pt_moments_variance", "pt_ctx_moments_variance", "pt_image_denoise", "pt_ctx_denoise", "pt_ctx_render_denoised",
+    "pt_image_temporal", "pt_ctx_temporal", "pt_ctx_render_temporal",
 )
 PT_MAX_DEVICES = 16
 
@@ -195,6 +196,41 @@ class pt_denoised_stats(C.Structure):
                 ("denoise", pt_denoise_stats)]
 
 
+class pt_temporal_history(C.Structure):
+    """The seven planes of an accumulated history (include/pt_hip.h)."""
+    NAMES = ("color", "m2", "var", "hist", "normal", "position", "cls")
+    WIDTH = {"color": 3, "m2": 3, "var": 3, "hist": 1, "normal": 3, "position": 3, "cls": 1}
+    INT = ("hist", "cls")
+    _fields_ = [(k, C.c_void_p) for k in NAMES]
+
+
+PT_TEMPORAL_VAR_SAMPLE, PT_TEMPORAL_VAR_TEMPORAL = 1, 2
+
+
+class pt_temporal_params(C.Structure):
+    """A 0 selects the default: max_history 32, sigma_z 0.01, normal_min 0.9, sample mode with a variance."""
+    _fields_ = [("max_history", C.c_int32), ("sigma_z", C.c_float), ("normal_min", C.c_float),
+                ("variance_mode", C.c_int32)]
+
+
+class pt_temporal_stats(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("total_ms", C.c_double), ("reused", C.c_int64)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class pt_render_temporal_stats(C.Structure):
+    _fields_ = [("total_ms", C.c_double), ("render_ms", C.c_double), ("aov_ms", C.c_double), ("variance_ms", C.c_double),
+                ("rays", C.c_uint64), ("had_history", C.c_int32), ("variance_mode", C.c_int32),
+                ("temporal", pt_temporal_stats), ("denoise", pt_denoise_stats)]
+
+    def as_dict(self) -> dict:
+        d = {k: getattr(self, k) for k, _ in self._fields_[:7]}
+        d.update(temporal=self.temporal.as_dict(), denoise=self.denoise.as_dict(), reused=self.temporal.reused)
+        return d
+
+
 class pt_aov(C.Structure):
     """First-hit channels (include/pt_hip.h); a NULL pointer skips the channel."""
     CHANNELS = ("t", "tri", "normal", "albedo", "emission", "ray")
@@ -204,6 +240,7 @@ class pt_aov(C.Structure):
 
 assert C.sizeof(pt_bvh_node) == 40 and C.sizeof(pt_material) == 32 and C.sizeof(pt_trace_stats) == 64
 assert C.sizeof(pt_denoise_params) == 20 and C.sizeof(pt_denoise_stats) == 96 and C.sizeof(pt_denoise_guides) == 40
+assert C.sizeof(pt_temporal_params) == 16 and C.sizeof(pt_temporal_stats) == 24 and C.sizeof(pt_temporal_history) == 56
 
 
 class PTError(RuntimeError):
@@ -322,6 +359,18 @@ def lib() -> C.CDLL:
             L.pt_ctx_render_denoised.argtypes = [P, C.POINTER(pt_camera), C.POINTER(pt_params), C.POINTER(pt_adaptive),
                                                  C.POINTER(pt_denoise_params), P, P, P, C.c_int,
                                                  C.POINTER(pt_adaptive_stats), C.POINTER(pt_denoised_stats)]
+        if hasattr(L, "pt_ctx_temporal"):  # absent from older builds used in A/B runs
+            L.pt_image_temporal.argtypes = [C.c_int32, C.c_int32, C.POINTER(pt_camera), C.POINTER(pt_camera), P, P,
+                                            C.POINTER(pt_denoise_guides), C.POINTER(pt_temporal_history),
+                                            C.POINTER(pt_temporal_history), C.POINTER(pt_temporal_params),
+                                            C.POINTER(C.c_int64)]
+            L.pt_ctx_temporal.argtypes = [P, C.c_int32, C.c_int32, C.POINTER(pt_camera), C.POINTER(pt_camera), P, P,
+                                          C.POINTER(pt_denoise_guides), C.POINTER(pt_temporal_history),
+                                          C.POINTER(pt_temporal_history), C.POINTER(pt_temporal_params), C.c_int,
+                                          C.POINTER(pt_temporal_stats)]
+            L.pt_ctx_render_temporal.argtypes = [P, C.POINTER(pt_camera), C.POINTER(pt_params),
+                                                 C.POINTER(pt_temporal_params), C.POINTER(pt_denoise_params), C.c_int,
+                                                 P, P, C.c_int, C.POINTER(pt_render_temporal_stats)]
         if hasattr(L, "pt_debug_rccl_failover"):  # test hooks (absent from older builds used in A/B runs)
             L.pt_debug_rccl_failover.argtypes = [C.c_int32, C.c_int32, P]
         if hasattr(L, "pt_debug_rtc_cache"):
