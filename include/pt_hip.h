@@ -800,6 +800,90 @@ int pt_ctx_trace_grad(pt_ctx* ctx, const float* origins, const float* dirs, int6
 int pt_bvh_trace_grad(const pt_scene* scene, const float* origins, const float* dirs, int64_t n,
                       const pt_trace_params* params, const pt_trace_grad_io* io, pt_grad_stats* stats);
 
+/* ---- light sampling (next-event estimation) -------------------------------------
+ * An opt-in estimator beside trace(): a diffuse vertex also samples a point on the emitters and
+ * tests its visibility with one extra closest-hit walk. Its expected value is trace()'s at every
+ * depth (below); every other entry point keeps its bits. All arithmetic is float32 with + - * /,
+ * fabsf and comparisons, each operation rounded on its own (no contraction, correctly rounded
+ * division), in the order written; csrc/pt_nee.h states it once for the host form and the kernels.
+ *
+ * Light table (made on the host per scene). The lights are the triangles j, in the caller's
+ * triangle order, whose material type is PT_MAT_EMIT, whose emit is finite with some channel > 0,
+ * and whose area a_j = 0.5f * sqrtf(dot(c, c)), c = cross(v2 - v1, v3 - v1), is finite and > 0.
+ * cdf_j is the running float32 sum of a_j from +0 and A its last entry. With no such triangle, or
+ * with A not finite, the scene has no lights: no light draw is made and no direct term is added.
+ * kA = A / 3.14159274f (A / (float)M_PI) is formed once.
+ *
+ * Path (i, s) in forward form: T = (1, 1, 1), L = (+0, +0, +0), sampled = false; the LCG state and
+ * the ray are pt_ctx_trace's. For k = 1 .. depth:
+ *   1. BVH::intersect. A miss ends the path.
+ *   2. An EMIT hit: L = L + T o emit, unless `sampled` is true and the triangle is in the light
+ *      table (then nothing is added). The path ends.
+ *   3. Any other hit: L = L + T o emit_h. n (faced as triangle.h:48), hp = o + d t and
+ *      new_o = hp + n * 1e-4f are trace()'s.
+ *   4. Light draw, when the material samples the hemisphere (every type but EMIT and SPECULAR),
+ *      the scene has lights and k < depth:
+ *        x1, x2, x3 = rand01() in this order, before the BRDF draw;
+ *        j = the first light with cdf_j > x1 * A, the last light when there is none;
+ *        (u, v) = (x2, x3), replaced by (1 - u, 1 - v) when u + v > 1;
+ *        y = (v1 + e1 * u) + e2 * v with e1 = v2 - v1, e2 = v3 - v1 of light j;
+ *        w = y - new_o, cx = dot(n, w), cy = fabsf(dot(n_j, w)) with n_j = normalize(cross(e1, e2))
+ *        (not faced), r2 = dot(w, w);
+ *        if cx > 0 && cy > 0 && r2 > 0 the shadow segment is walked: BVH::intersect of the ray
+ *        (new_o, w), w unnormalised; the light is visible exactly when that hit's triangle index
+ *        (the caller's numbering) is j, and then
+ *            L = L + ((T o color_h) o emit_j) * (((cx / r2) * (cy / r2)) * kA);
+ *        sampled = true, whether or not a shadow segment ran.
+ *      Without a light draw, sampled = false.
+ *   5. k == depth ends the path (the reference's last BRDF draw cannot be observed and is not made).
+ *   6. new_d by Material::reflected_dir with trace()'s draws and its bound on the specular
+ *      rejection loop; c = dot(n, new_d); T = ((2 * T) o color_h) * c; the ray becomes (new_o, new_d).
+ * dot is (x x + y y) + z z and `o` the per-channel product, as everywhere in this header.
+ *
+ * Expectation. At a vertex that samples the hemisphere uniformly, trace()'s term
+ * 2 cos rho Le(first hit) is the area integral of rho / pi * Le * cosx cosy / r^2 * V over the
+ * emitters; step 4 estimates that integral with density 1 / A, and the EMIT hit it replaces is
+ * dropped by `sampled`. The connection at hit k stands for an EMIT hit at k + 1, so it runs for
+ * k < depth only and the depth cut is the same. Emission of other materials, unlisted EMIT
+ * triangles and everything after a SPECULAR bounce stay with BRDF sampling.
+ * Not in this definition: multiple importance sampling (an emitter touching a diffuse surface
+ * gives a heavy-tailed 1 / r^2 term), Russian roulette, light sampling at SPECULAR vertices.
+ *
+ * The per-ray result is pt_ctx_trace's: the float32 sum over samples in order from +0, / spp. */
+typedef struct pt_nee_stats {    /* 88 bytes */
+    pt_trace_stats trace;        /* as pt_ctx_trace fills it; trace.rays counts path AND shadow segments */
+    uint64_t shadow_rays;        /* shadow segments walked */
+    uint64_t light_draws;        /* vertices that drew a light (step 4) */
+    int32_t lights;              /* rows of the light table */
+    float light_area;            /* A (0 without lights) */
+} pt_nee_stats;
+
+/* The light table of a scene (validated as by pt_scene_validate): *count = its rows, *area = A
+ * (0 rows and 0.0f without lights); the first min(*count, cap) rows go to tri_out (the caller's
+ * triangle indices) and cdf_out, either of which may be NULL. */
+int pt_scene_lights(const pt_scene* scene, int32_t* tri_out, float* cdf_out, int64_t cap, int64_t* count,
+                    float* area);
+
+/* The estimator on the host over the caller's own arrays (no device needed), bit-identical to
+ * pt_ctx_trace_nee. Arguments as pt_bvh_trace. */
+int pt_bvh_trace_nee(const pt_scene* scene, const float* origins, const float* dirs, int64_t n,
+                     const pt_trace_params* params, float* rgb_out, pt_nee_stats* stats);
+
+/* The estimator for n rays on the context's scene; pointers, launch cuts, PT_E_RUNAWAY and
+ * synchronisation as pt_ctx_trace. Uses buffers of its own and leaves a running sum valid. */
+int pt_ctx_trace_nee(pt_ctx* ctx, const float* origins, const float* dirs, int64_t n,
+                     const pt_trace_params* params, float* rgb_out, int is_device, pt_nee_stats* stats);
+
+/* The estimator along the render's own camera rays: sample s of pixel p starts the LCG at
+ * pt_sample_seed(p, s, seed) and makes Camera::get_ray's two draws first, so its first hits are
+ * pt_ctx_render_aov's. img_out (rows*W*3) receives the float32 sum of params->spp samples in sample
+ * order, / spp; `moments` (optional, every pointer optional) the sums S, Q and sem of those
+ * samples as pt_ctx_render_moments defines them. The part fields work as in pt_ctx_render;
+ * batch_spp and samples_per_item are not read. One-shot: there is no continuation, and the call
+ * ends a running sum, as any render does. is_device covers img_out and the pointers of moments. */
+int pt_ctx_render_nee(pt_ctx* ctx, const pt_camera* cam, const pt_params* params, float* img_out,
+                      const pt_moments* moments, int is_device, pt_nee_stats* stats);
+
 /* Number of rows of part `part_index` for the given partition. */
 int32_t pt_part_rows(int32_t res_y, int32_t part_index, int32_t part_count, int32_t band_rows);
 

@@ -29,6 +29,7 @@
 #include "pt_denoise.h"
 #include "pt_temporal.h"
 #include "pt_moments.h"
+#include "pt_nee.h"
 
 namespace pt {
 
@@ -1076,6 +1077,43 @@ int pt::temporal_check(const char* who, int32_t W, int32_t H, const pt_camera* c
     return PT_OK;
 }
 
+// The light table (pt_hip.h: the definition) from the caller's arrays of a validated scene.
+void pt::scene_light_table(const pt_scene* s, LightTable& out) {
+    out = LightTable();
+    out.listed.assign((size_t)s->num_tris, 0);
+    float run = 0.0f;
+    for (int32_t j = 0; j < s->num_tris; j++) {
+        const pt_material& m = s->materials[j];
+        if (m.type != PT_MAT_EMIT) continue;
+        const v3 e{m.emit[0], m.emit[1], m.emit[2]};
+        if (!all_finite(e) || !(e.x > 0.0f || e.y > 0.0f || e.z > 0.0f)) continue;
+        const float* v = s->verts + 9 * (size_t)j;
+        const v3 v1{v[0], v[1], v[2]};
+        const v3 e1 = sub(v3{v[3], v[4], v[5]}, v1), e2 = sub(v3{v[6], v[7], v[8]}, v1);
+        const v3 c = cross(e1, e2);
+        const float a = 0.5f * sqrtf(dot(c, c));
+        if (!(fabsf(a) < INFINITY) || !(a > 0.0f)) continue;
+        const v3 nl = normalize(c);
+        run = run + a;
+        out.tri.push_back(j);
+        out.cdf.push_back(run);
+        out.geom.push_back(f4{v1.x, v1.y, v1.z, 0.0f});
+        out.geom.push_back(f4{e1.x, e1.y, e1.z, 0.0f});
+        out.geom.push_back(f4{e2.x, e2.y, e2.z, 0.0f});
+        out.geom.push_back(f4{nl.x, nl.y, nl.z, 0.0f});
+        out.geom.push_back(f4{e.x, e.y, e.z, 0.0f});
+        out.listed[(size_t)j] = 1;
+    }
+    if (out.tri.empty() || !(fabsf(run) < INFINITY)) {  // no lights
+        const size_t n = out.listed.size();
+        out = LightTable();
+        out.listed.assign(n, 0);
+        return;
+    }
+    out.area = run;
+    out.kA = run / (float)M_PI;
+}
+
 extern "C" {
 
 int pt_abi_version(void) { return PT_ABI_VERSION; }
@@ -1240,6 +1278,134 @@ int pt_bvh_trace(const pt_scene* scene, const float* origins, const float* dirs,
         stats->paths = (uint64_t)n * (uint64_t)spp;
         stats->runaway = runaway;
         stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    }
+    if (runaway != 0)
+        return set_error(PT_E_RUNAWAY, "%llu specular rejection loops hit the %d-iteration bound",
+                         (unsigned long long)runaway, kSpecularIterBound);
+    return PT_OK;
+}
+
+int pt_scene_lights(const pt_scene* scene, int32_t* tri_out, float* cdf_out, int64_t cap, int64_t* count, float* area) {
+    if (count) *count = 0;
+    if (area) *area = 0.0f;
+    if (cap < 0) return set_error(PT_E_ARG, "pt_scene_lights: cap = %lld is negative", (long long)cap);
+    PackedScene ps;
+    const int rc = pack_scene(scene, ps);  // pt_scene_validate's checks
+    if (rc) return rc;
+    LightTable lt;
+    scene_light_table(scene, lt);
+    const int64_t n = std::min<int64_t>(cap, (int64_t)lt.tri.size());
+    for (int64_t i = 0; i < n; i++) {
+        if (tri_out) tri_out[i] = lt.tri[(size_t)i];
+        if (cdf_out) cdf_out[i] = lt.cdf[(size_t)i];
+    }
+    if (count) *count = (int64_t)lt.tri.size();
+    if (area) *area = lt.area;
+    return PT_OK;
+}
+
+// The light-sampling estimator (pt_hip.h: the definition) for a batch of the caller's rays on the
+// host, with the arithmetic of the kernels (pt_nee.h): pt_bvh_trace's walk for path and shadow
+// segments alike, the path in forward form, and the per-ray sum in sample order.
+int pt_bvh_trace_nee(const pt_scene* scene, const float* origins, const float* dirs, int64_t n, const pt_trace_params* prm,
+                     float* rgb_out, pt_nee_stats* stats) {
+    const auto t_start = std::chrono::steady_clock::now();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!prm) return set_error(PT_E_ARG, "pt_bvh_trace_nee: params is NULL");
+    if (n < 0) return set_error(PT_E_ARG, "pt_bvh_trace_nee: n = %lld is negative", (long long)n);
+    if (prm->depth < 0 || prm->depth > PT_MAX_DEPTH)
+        return set_error(PT_E_ARG, "pt_bvh_trace_nee: depth %d outside 0..%d", prm->depth, PT_MAX_DEPTH);
+    if (prm->spp < 1 || prm->spp > kTraceMaxSpp)
+        return set_error(PT_E_ARG, "pt_bvh_trace_nee: spp %d outside 1..%d", prm->spp, kTraceMaxSpp);
+    PackedScene ps;
+    const int rc = pack_scene(scene, ps);  // pt_scene_validate's checks: the walk cannot leave the arrays
+    if (rc) return rc;
+    if (n == 0) return PT_OK;
+    if (!origins || !dirs || !rgb_out) return set_error(PT_E_ARG, "pt_bvh_trace_nee: NULL argument");
+    LightTable lt;
+    scene_light_table(scene, lt);
+    const int nl = (int)lt.tri.size();
+    std::vector<int32_t> stack;
+    stack.reserve((size_t)ps.stack_size + 1);
+    const int depth = prm->depth, spp = prm->spp;
+    uint64_t rays = 0, runaway = 0, shadow = 0, draws = 0;
+    for (int64_t r = 0; r < n; r++) {
+        float sum[3] = {0.0f, 0.0f, 0.0f};
+        for (int s = 0; s < spp; s++) {
+            Lcg g{prm->states ? prm->states[(size_t)r * spp + s] : pt_sample_seed((uint32_t)r, (uint32_t)s, prm->seed)};
+            v3 o{origins[3 * r], origins[3 * r + 1], origins[3 * r + 2]};
+            v3 d{dirs[3 * r], dirs[3 * r + 1], dirs[3 * r + 2]};
+            v3 T{1.0f, 1.0f, 1.0f}, L{0.0f, 0.0f, 0.0f};
+            bool sampled = false;
+            for (int k = 1; k <= depth; k++) {
+                float t;
+                rays++;
+                const int32_t ti = walk_ray(scene, stack, o, d, t);
+                if (ti < 0) break;
+                const pt_material& m = scene->materials[ti];
+                const v3 emit{m.emit[0], m.emit[1], m.emit[2]};
+                if (m.type == PT_MAT_EMIT) {
+                    if (!(sampled && lt.listed[(size_t)ti])) L = nee_add_emit(L, T, emit);
+                    break;
+                }
+                L = nee_add_emit(L, T, emit);
+                const v3 color{m.color[0], m.color[1], m.color[2]};
+                const float* v = scene->verts + 9 * (size_t)ti;
+                const v3 v1{v[0], v[1], v[2]};
+                v3 nrm = normalize(cross(sub(v3{v[3], v[4], v[5]}, v1), sub(v3{v[6], v[7], v[8]}, v1)));
+                if (!(dot(nrm, d) < 0.0f)) nrm = neg(nrm);  // triangle.h:48
+                const v3 hp = add(o, scale(d, t));
+                const v3 no = add(hp, scale(nrm, 1e-4f));  // SHIFT_BIAS, render.h:16, 52
+                sampled = m.type != PT_MAT_SPECULAR && nl > 0 && k < depth;
+                if (sampled) {
+                    draws++;
+                    const float x1 = g.next01();
+                    const float x2 = g.next01();
+                    const float x3 = g.next01();
+                    const int j = nee_pick(lt.cdf.data(), nl, x1 * lt.area);
+                    const f4* G = lt.geom.data() + (size_t)kNeeLightF4 * j;
+                    const v3 y = nee_point(v3{G[0].x, G[0].y, G[0].z}, v3{G[1].x, G[1].y, G[1].z},
+                                           v3{G[2].x, G[2].y, G[2].z}, x2, x3);
+                    v3 w;
+                    float gw;
+                    if (nee_connect(y, no, nrm, v3{G[3].x, G[3].y, G[3].z}, lt.kA, w, gw)) {
+                        float ts;
+                        rays++;
+                        shadow++;
+                        if (walk_ray(scene, stack, no, w, ts) == lt.tri[(size_t)j])
+                            L = add(L, nee_direct(T, color, v3{G[4].x, G[4].y, G[4].z}, gw));
+                    }
+                }
+                if (k == depth) break;
+                v3 nd;
+                if (m.type == PT_MAT_SPECULAR) {
+                    if (!specular_dir(g, d, nrm, m.roughness, kSpecularIterBound, nd)) runaway++;
+                } else {
+                    nd = hemisphere_dir(g, nrm);
+                }
+                T = nee_throughput(T, color, dot(nrm, nd));
+                o = no;
+                d = nd;
+            }
+            sum[0] = sum[0] + L.x;  // image.h:27-31
+            sum[1] = sum[1] + L.y;
+            sum[2] = sum[2] + L.z;
+        }
+        const float fs = (float)spp;
+        rgb_out[3 * r] = sum[0] / fs;  // image.h:37-40
+        rgb_out[3 * r + 1] = sum[1] / fs;
+        rgb_out[3 * r + 2] = sum[2] / fs;
+    }
+    if (stats) {
+        stats->trace.rays = rays;
+        stats->trace.paths = (uint64_t)n * (uint64_t)spp;
+        stats->trace.runaway = runaway;
+        stats->trace.total_ms =
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+        stats->shadow_rays = shadow;
+        stats->light_draws = draws;
+        stats->lights = nl;
+        stats->light_area = lt.area;
     }
     if (runaway != 0)
         return set_error(PT_E_RUNAWAY, "%llu specular rejection loops hit the %d-iteration bound",

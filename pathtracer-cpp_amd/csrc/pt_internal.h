@@ -188,6 +188,34 @@ struct PathsLaunch {
 };
 int paths_launch(void* stream, const QueryScene& sc, const WalkPlan& plan, const PathsLaunch& l);
 
+// ---- light sampling (pt_nee.h, pt_nee.hip; the host form is in pt_host.cpp, the entry points in pt_kernel.hip) ----
+// The light table of a scene (include/pt_hip.h: the definition), made on the host by
+// scene_light_table (pt_host.cpp) from the caller's arrays of a validated scene.
+constexpr int kNeeLightF4 = 5;  // float4 per light in the geometry rows
+struct LightTable {
+    std::vector<int32_t> tri;     // the caller's triangle index of each light
+    std::vector<float> cdf;       // running float32 sum of the areas; A = cdf.back()
+    std::vector<f4> geom;         // kNeeLightF4 rows per light: v1, e1, e2, unit normal, emit_color (w = 0)
+    std::vector<uint8_t> listed;  // per caller triangle: 1 when it is a light
+    float area = 0.0f, kA = 0.0f; // A and A / (float)M_PI; both 0 without lights
+};
+void scene_light_table(const pt_scene* s, LightTable& out);
+// The table on a device (pt_kernel.hip uploads it on the first light-sampling call after a scene is set).
+struct NeeLights {
+    const float* cdf;
+    const int32_t* tri;
+    const f4* geom;
+    const uint8_t* listed;
+    int32_t count;
+    float area, kA;
+};
+// paths_plan for the light-sampling kernels (no path records); camera: the part's camera rays.
+int nee_plan(bool camera, const QueryScene& sc, size_t lds_usable, int num_cus, int64_t items, WalkPlan& plan);
+// One launch over l.m rays (or, with cam, the first l.m pixels of the part) x l.spp samples from
+// sample s_begin; l.ctr: 6 zeroed u64, [4] shadow segments and [5] light draws added. l.grec is not read.
+int nee_launch(void* stream, const QueryScene& sc, const WalkPlan& plan, const PathsLaunch& l, const NeeLights& lights,
+               int32_t s_begin, const pt_camera* cam, const pt_params* prm, const PartShape* shape);
+
 // ---- per-pixel rounds of pt_ctx_render_adaptive (pt_adaptive.hip; the host loop is in pt_kernel.hip) ----
 // All on `stream` (a hipStream_t), device pointers, no synchronisation. Lists hold part-local pixel indices.
 // paths_plan for the kernel fed from a list; `items`: listed pixels x samples of the largest launch.

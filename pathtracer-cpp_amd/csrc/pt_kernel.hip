@@ -382,6 +382,13 @@ struct pt_ctx {
     float* d_tstates = nullptr;              // staging of a host-pointer call's LCG states (uint32)
     size_t tstates_words = 0;
     unsigned long long* d_tctr = nullptr;    // work head, ray and runaway counters of a call (4 x u64)
+    // light sampling (pt_ctx_trace_nee, pt_ctx_render_nee; pt_nee.hip): the scene's light table, made on the
+    // host when the scene is set and uploaded by the first call that samples lights; pt_ctx_trace's staging
+    LightTable lights;
+    bool lights_uploaded = false;
+    uint8_t* d_lights = nullptr;             // [geom 5 x float4][cdf][tri][listed per caller triangle]
+    size_t lights_bytes = 0;
+    unsigned long long* d_nctr = nullptr;    // d_tctr's four counters, then shadow segments and light draws
     // material gradients (pt_ctx_trace_grad): pt_ctx_trace's buffers, and
     double* d_gtab = nullptr;                // the gradient table, 6 doubles per caller triangle, then the split outputs
     size_t gtab_doubles = 0;
@@ -1412,6 +1419,7 @@ void pt_ctx_destroy(pt_ctx* c) {
                     (void*)c->d_accum, (void*)c->d_out, (void*)c->d_ctr, (void*)c->d_stamps, (void*)c->d_rgb8, (void*)c->d_thr, (void*)c->d_xstack,
                     (void*)c->d_rank_tri, (void*)c->d_qstack, (void*)c->d_qbuf, (void*)c->d_qhits,
                     (void*)c->d_tslab, (void*)c->d_trec, (void*)c->d_tbuf, (void*)c->d_tstates, (void*)c->d_tctr,
+                    (void*)c->d_lights, (void*)c->d_nctr,
                     (void*)c->d_gtab, (void*)c->d_gmats, (void*)c->d_gbuf, (void*)c->d_mom, (void*)c->d_mcount, (void*)c->d_sem,
                     (void*)c->d_alist[0], (void*)c->d_alist[1], (void*)c->d_aspp, (void*)c->d_aslab, (void*)c->d_arec, (void*)c->d_actr})
         if (p) (void)hipFree(p);
@@ -1453,6 +1461,7 @@ int pt_ctx_set_scene(pt_ctx* c, const pt_scene* scene) {
     c->have_scene = false;
     c->prog_valid = false;
     c->temporal.valid = false;
+    c->lights_uploaded = false, scene_light_table(scene, c->lights);  // the light table of pt_ctx_*_nee
     HIP_TRY(hipMalloc((void**)&c->d_nodes, ps.nodes.size() * sizeof(float4)));
     HIP_TRY(hipMalloc((void**)&c->d_tris, ps.tris.size() * sizeof(float4)));
     HIP_TRY(hipMalloc((void**)&c->d_mats, ps.mats.size() * sizeof(float4)));
@@ -1938,6 +1947,295 @@ int pt_ctx_trace(pt_ctx* c, const float* origins, const float* dirs, int64_t n, 
     HIP_TRY(hipMemcpyAsync(h_ctr, c->d_tctr, sizeof(h_ctr), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     finish(&plan, h_ctr, kernel_ms, reduce_ms, launches);
+    if (h_ctr[3] != 0)
+        return set_error(PT_E_RUNAWAY, "%llu specular rejection loops hit the %d-iteration bound", h_ctr[3],
+                         kMaxSpecularIters);
+    return PT_OK;
+}
+
+// ---- light sampling (pt_nee.hip)
+// The context's light table on its device: uploaded by the first call after pt_ctx_set_scene.
+static int nee_lights(pt_ctx* c, NeeLights* out) {
+    const LightTable& lt = c->lights;
+    const size_t nl = lt.tri.size();
+    *out = NeeLights{nullptr, nullptr, nullptr, nullptr, 0, 0.0f, 0.0f};
+    if (nl == 0) return PT_OK;
+    const size_t geom_b = nl * kNeeLightF4 * sizeof(f4), word_b = nl * sizeof(float);
+    if (!c->lights_uploaded) {
+        if (int rc = ensure(&c->d_lights, &c->lights_bytes, geom_b + 2 * word_b + lt.listed.size())) return rc;
+        HIP_TRY(hipMemcpyAsync(c->d_lights, lt.geom.data(), geom_b, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->d_lights + geom_b, lt.cdf.data(), word_b, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->d_lights + geom_b + word_b, lt.tri.data(), word_b, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->d_lights + geom_b + 2 * word_b, lt.listed.data(), lt.listed.size(), hipMemcpyHostToDevice,
+                               c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        c->lights_uploaded = true;
+    }
+    out->geom = reinterpret_cast<const f4*>(c->d_lights);
+    out->cdf = reinterpret_cast<const float*>(c->d_lights + geom_b);
+    out->tri = reinterpret_cast<const int32_t*>(c->d_lights + geom_b + word_b);
+    out->listed = c->d_lights + geom_b + 2 * word_b;
+    out->count = (int32_t)nl;
+    out->area = lt.area;
+    out->kA = lt.kA;
+    return PT_OK;
+}
+
+// What both entry points launch with: the plan's global stack, the six zeroed counters, and the
+// fields of a launch that do not change from one launch to the next.
+static int nee_setup(pt_ctx* c, const WalkPlan& plan, int32_t spp, int32_t depth, uint32_t seed, PathsLaunch& l) {
+    int rc;
+    if (plan.stack_ints > 0 && (rc = ensure(&c->d_qstack, &c->qstack_ints, plan.stack_ints))) return rc;
+    if (!c->d_nctr) HIP_TRY(hipMalloc((void**)&c->d_nctr, 6 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(c->d_nctr, 0, 6 * sizeof(unsigned long long), c->stream));
+    l = PathsLaunch{};
+    l.spp = spp;
+    l.depth = depth;
+    l.seed = seed;
+    l.slab = c->d_tslab;
+    l.ctr = c->d_nctr;
+    l.gstack = c->d_qstack;
+    l.grec = nullptr;
+    l.dark = 0;
+    l.force_exact = query_force_exact();
+    const float2* tab = nullptr;
+    if ((rc = theta_choice(c, &l.theta_lanes, &tab))) return rc;
+    l.theta_tab = tab;
+    return PT_OK;
+}
+
+static void nee_stats(pt_nee_stats* stats, const pt_ctx* c, const WalkPlan* plan, const unsigned long long* ctr, uint64_t paths,
+                      double kms, double rms, int launches, std::chrono::steady_clock::time_point t_start) {
+    if (!stats) return;
+    stats->trace.rays = ctr[1];
+    stats->trace.paths = paths;
+    stats->trace.runaway = ctr[3];
+    stats->trace.kernel_ms = kms;
+    stats->trace.reduce_ms = rms;
+    stats->trace.launches = launches;
+    if (plan) {
+        stats->trace.lds_scene = plan->lds_scene;
+        stats->trace.lds_stack = plan->lds_stack;
+    }
+    stats->trace.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    stats->shadow_rays = ctr[4];
+    stats->light_draws = ctr[5];
+    stats->lights = (int32_t)c->lights.tri.size();
+    stats->light_area = c->lights.area;
+}
+
+// pt_ctx_trace with pt_nee_kernel in place of pt_paths_kernel: the same cuts over rays
+// (PT_TRACE_CHUNK, test hook: rays per launch), staging and in-order sum; the counters are its own.
+int pt_ctx_trace_nee(pt_ctx* c, const float* origins, const float* dirs, int64_t n, const pt_trace_params* prm,
+                     float* rgb_out, int is_device, pt_nee_stats* stats) {
+    const auto t_start = std::chrono::steady_clock::now();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!c) return set_error(PT_E_ARG, "pt_ctx_trace_nee: context is NULL");
+    if (!prm) return set_error(PT_E_ARG, "pt_ctx_trace_nee: params is NULL");
+    if (n < 0) return set_error(PT_E_ARG, "pt_ctx_trace_nee: n = %lld is negative", (long long)n);
+    if (prm->depth < 0 || prm->depth > PT_MAX_DEPTH)
+        return set_error(PT_E_ARG, "pt_ctx_trace_nee: depth %d outside 0..%d", prm->depth, PT_MAX_DEPTH);
+    if (prm->spp < 1 || prm->spp > kTraceMaxSpp)
+        return set_error(PT_E_ARG, "pt_ctx_trace_nee: spp %d outside 1..%d", prm->spp, kTraceMaxSpp);
+    if (!c->have_scene) return set_error(PT_E_ARG, "pt_ctx_trace_nee: no scene set");
+    if (n == 0) return PT_OK;
+    if (!origins || !dirs || !rgb_out) return set_error(PT_E_ARG, "pt_ctx_trace_nee: NULL argument");
+    if (int rc0 = ctx_ready(c)) return rc0;
+    HIP_TRY(hipSetDevice(c->device));
+    const int64_t spp = prm->spp;
+    if (prm->depth == 0) {  // no segment is walked: every path returns +0
+        if (is_device) {
+            HIP_TRY(hipMemsetAsync(rgb_out, 0, 3 * sizeof(float) * (size_t)n, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+        } else {
+            memset(rgb_out, 0, 3 * sizeof(float) * (size_t)n);
+        }
+        const unsigned long long zero[6] = {0, 0, 0, 0, 0, 0};
+        nee_stats(stats, c, nullptr, zero, (uint64_t)n * (uint64_t)spp, 0, 0, 0, t_start);
+        return PT_OK;
+    }
+    // rays per launch
+    int64_t m_max = std::min<int64_t>(n, ((1ll << 31) - 1) / spp);
+    m_max = std::min<int64_t>(m_max, (int64_t)(batch_bytes_budget(c->device, false) / (3 * sizeof(float) * (size_t)spp)));
+    if (!is_device) m_max = std::min(m_max, kQueryHostChunk);
+    if (const char* tc = hook_env("PT_TRACE_CHUNK"))
+        if (*tc) m_max = std::min<int64_t>(m_max, strtoll(tc, nullptr, 10));
+    m_max = std::max<int64_t>(m_max, 1);
+    const QueryScene sc = query_scene(c);
+    NeeLights lights;
+    WalkPlan plan;
+    PathsLaunch l;
+    int rc;
+    if ((rc = nee_lights(c, &lights))) return rc;
+    if ((rc = nee_plan(false, sc, c->lds_usable, c->num_cus, m_max * spp, plan))) return rc;
+    if ((rc = ensure(&c->d_tslab, &c->tslab_floats, 3 * (size_t)(m_max * spp)))) return rc;
+    if ((rc = nee_setup(c, plan, (int32_t)spp, prm->depth, prm->seed, l))) return rc;
+    // host pointers: staging [origins 3][dirs 3][rgb 3] x m_max, and the states
+    float *s_org = nullptr, *s_dir = nullptr, *s_out = nullptr;
+    if (!is_device) {
+        if ((rc = ensure(&c->d_tbuf, &c->tbuf_floats, 9 * (size_t)m_max))) return rc;
+        s_org = c->d_tbuf;
+        s_dir = s_org + 3 * m_max;
+        s_out = s_dir + 3 * m_max;
+        if (prm->states && (rc = ensure(&c->d_tstates, &c->tstates_words, (size_t)(m_max * spp)))) return rc;
+    }
+    EventPair ev, ev2;
+    HIP_TRY(hipEventCreate(&ev.a));
+    HIP_TRY(hipEventCreate(&ev.b));
+    HIP_TRY(hipEventCreate(&ev2.a));
+    double kernel_ms = 0, reduce_ms = 0;
+    int launches = 0;
+    for (int64_t i0 = 0; i0 < n; i0 += m_max) {
+        const int32_t m = (int32_t)std::min(m_max, n - i0);
+        l.m = m;
+        l.ray_base = (uint32_t)i0;
+        l.org = origins + 3 * i0;
+        l.dir = dirs + 3 * i0;
+        l.states = prm->states ? prm->states + i0 * spp : nullptr;
+        float* k_out = rgb_out + 3 * i0;
+        if (!is_device) {
+            HIP_TRY(hipMemcpyAsync(s_org, l.org, 3 * sizeof(float) * (size_t)m, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(s_dir, l.dir, 3 * sizeof(float) * (size_t)m, hipMemcpyHostToDevice, c->stream));
+            if (prm->states) {
+                HIP_TRY(hipMemcpyAsync(c->d_tstates, l.states, sizeof(uint32_t) * (size_t)(m * spp), hipMemcpyHostToDevice,
+                                       c->stream));
+                l.states = reinterpret_cast<const uint32_t*>(c->d_tstates);
+            }
+            l.org = s_org;
+            l.dir = s_dir;
+            k_out = s_out;
+        }
+        HIP_TRY(hipMemsetAsync(c->d_nctr, 0, sizeof(unsigned long long), c->stream));  // work head only
+        HIP_TRY(hipEventRecord(ev.a, c->stream));
+        if ((rc = nee_launch(c->stream, sc, plan, l, lights, 0, nullptr, nullptr, nullptr))) return rc;
+        HIP_TRY(hipEventRecord(ev.b, c->stream));
+        // the ray's samples in order from +0, then / spp (image.h:27-31, 37-40)
+        hipLaunchKernelGGL(pt_accumulate_kernel, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->d_tslab,
+                           (float*)nullptr, k_out, (int)m, (int)spp, 1, 1, 0, (float)spp, (const uint32_t*)nullptr, 0);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(ev2.a, c->stream));
+        launches++;
+        if (!is_device)
+            HIP_TRY(hipMemcpyAsync(rgb_out + 3 * i0, s_out, 3 * sizeof(float) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
+        kernel_ms += ms;
+        HIP_TRY(hipEventElapsedTime(&ms, ev.b, ev2.a));
+        reduce_ms += ms;
+    }
+    unsigned long long h_ctr[6] = {0, 0, 0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h_ctr, c->d_nctr, sizeof(h_ctr), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    nee_stats(stats, c, &plan, h_ctr, (uint64_t)n * (uint64_t)spp, kernel_ms, reduce_ms, launches, t_start);
+    if (h_ctr[3] != 0)
+        return set_error(PT_E_RUNAWAY, "%llu specular rejection loops hit the %d-iteration bound", h_ctr[3],
+                         kMaxSpecularIters);
+    return PT_OK;
+}
+
+// The estimator along the part's own camera rays: pt_nee_cam_kernel fills a dense slab
+// [sample][pixel][rgb] of one launch, and the render's accumulation passes sum a pixel's samples
+// in order (pt_accumulate_kernel; with moments pt_accumulate_moments_kernel). Launches are cut over
+// samples: c samples with npix * c < 2^31 records inside the slab budget (PT_NEE_CHUNK, test hook:
+// samples per launch). The sums use the render's buffers, so a running sum ends here.
+int pt_ctx_render_nee(pt_ctx* c, const pt_camera* cam, const pt_params* prm, float* img_out, const pt_moments* mom,
+                      int is_device, pt_nee_stats* stats) {
+    const auto t_start = std::chrono::steady_clock::now();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!c || !cam || !prm || !img_out) return set_error(PT_E_ARG, "pt_ctx_render_nee: NULL argument");
+    if (prm->spp < 1) return set_error(PT_E_ARG, "pt_ctx_render_nee: spp %d", prm->spp);
+    if (!c->have_scene) return set_error(PT_E_ARG, "pt_ctx_render_nee: no scene set");
+    PartShape shape;
+    int rc;
+    if ((rc = part_shape(cam, prm, PT_MAX_DEPTH, &shape))) return rc;
+    c->prog_valid = false;
+    const int npix = shape.npix, spp = prm->spp;
+    if (npix == 0) return PT_OK;
+    if ((rc = ctx_ready(c))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const bool moments = mom && (mom->sum || mom->sumsq || mom->sem);
+    const size_t nval = 3 * (size_t)npix;
+    if ((rc = ensure(&c->d_accum, &c->accum_floats, nval))) return rc;
+    if (moments && (rc = ensure(&c->d_mom, &c->mom_doubles, 2 * nval))) return rc;
+    if (!is_device && (rc = ensure(&c->d_out, &c->out_floats, nval))) return rc;
+    float* dst = is_device ? img_out : c->d_out;
+    // samples per launch
+    int64_t c_max = std::min<int64_t>(spp, ((1ll << 31) - 1) / npix);
+    c_max = std::min<int64_t>(c_max, (int64_t)(std::min<size_t>(batch_bytes_budget(c->device, false), (size_t)4 << 30) /
+                                               (sizeof(float) * nval)));
+    if (const char* nc = hook_env("PT_NEE_CHUNK"))
+        if (*nc) c_max = std::min<int64_t>(c_max, strtoll(nc, nullptr, 10));
+    c_max = std::max<int64_t>(c_max, 1);
+    const QueryScene sc = query_scene(c);
+    NeeLights lights;
+    WalkPlan plan;
+    PathsLaunch l;
+    unsigned long long h_ctr[6] = {0, 0, 0, 0, 0, 0};
+    double kernel_ms = 0, reduce_ms = 0;
+    int launches = 0;
+    EventPair ev, ev2;
+    HIP_TRY(hipEventCreate(&ev.a));
+    HIP_TRY(hipEventCreate(&ev.b));
+    HIP_TRY(hipEventCreate(&ev2.a));
+    const auto accumulate = [&](int count, int first, int last) {
+        if (moments)
+            hipLaunchKernelGGL(pt_accumulate_moments_kernel, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream,
+                               c->d_tslab, c->d_accum, dst, c->d_mom, npix, count, first, last, (float)spp,
+                               (const uint32_t*)nullptr, 0);
+        else
+            hipLaunchKernelGGL(pt_accumulate_kernel, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->d_tslab,
+                               c->d_accum, dst, npix, count, first, last, 0, (float)spp, (const uint32_t*)nullptr, 0);
+    };
+    if (prm->depth == 0) {  // no segment is walked: every sample is +0
+        if ((rc = ensure(&c->d_tslab, &c->tslab_floats, 1))) return rc;
+        // spp zero records would give the same sums: S = Q = +0, the image +0 / spp
+        accumulate(0, 1, 1);
+        HIP_TRY(hipGetLastError());
+    } else {
+        if ((rc = nee_lights(c, &lights))) return rc;
+        if ((rc = nee_plan(true, sc, c->lds_usable, c->num_cus, (int64_t)npix * c_max, plan))) return rc;
+        if ((rc = ensure(&c->d_tslab, &c->tslab_floats, nval * (size_t)c_max))) return rc;
+        if ((rc = nee_setup(c, plan, 0, prm->depth, prm->seed, l))) return rc;
+        l.m = npix;
+        for (int s0 = 0; s0 < spp; s0 += (int)c_max) {
+            const int sc_n = (int)std::min<int64_t>(c_max, spp - s0);
+            l.spp = sc_n;
+            HIP_TRY(hipMemsetAsync(c->d_nctr, 0, sizeof(unsigned long long), c->stream));  // work head only
+            HIP_TRY(hipEventRecord(ev.a, c->stream));
+            if ((rc = nee_launch(c->stream, sc, plan, l, lights, s0, cam, prm, &shape))) return rc;
+            HIP_TRY(hipEventRecord(ev.b, c->stream));
+            accumulate(sc_n, s0 == 0 ? 1 : 0, s0 + sc_n == spp ? 1 : 0);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(ev2.a, c->stream));
+            launches++;
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            float ms = 0;
+            HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
+            kernel_ms += ms;
+            HIP_TRY(hipEventElapsedTime(&ms, ev.b, ev2.a));
+            reduce_ms += ms;
+        }
+        HIP_TRY(hipMemcpyAsync(h_ctr, c->d_nctr, sizeof(h_ctr), hipMemcpyDeviceToHost, c->stream));
+    }
+    // the image and the moments to the caller (moments_export's copies, with n = spp)
+    const hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (!is_device) HIP_TRY(hipMemcpyAsync(img_out, dst, sizeof(float) * nval, hipMemcpyDeviceToHost, c->stream));
+    if (moments) {
+        if (mom->sum) HIP_TRY(hipMemcpyAsync(mom->sum, c->d_mom, nval * sizeof(double), kind, c->stream));
+        if (mom->sumsq) HIP_TRY(hipMemcpyAsync(mom->sumsq, c->d_mom + nval, nval * sizeof(double), kind, c->stream));
+        if (mom->sem) {
+            if (!is_device && (rc = ensure(&c->d_sem, &c->sem_floats, nval))) return rc;
+            float* sem = is_device ? mom->sem : c->d_sem;
+            hipLaunchKernelGGL(pt_moments_sem_kernel, dim3((unsigned)((nval + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
+                               c->d_mom, nval, spp, sem);
+            HIP_TRY(hipGetLastError());
+            if (!is_device) HIP_TRY(hipMemcpyAsync(mom->sem, sem, nval * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    nee_stats(stats, c, prm->depth > 0 ? &plan : nullptr, h_ctr, (uint64_t)npix * (uint64_t)spp, kernel_ms, reduce_ms, launches,
+              t_start);
     if (h_ctr[3] != 0)
         return set_error(PT_E_RUNAWAY, "%llu specular rejection loops hit the %d-iteration bound", h_ctr[3],
                          kMaxSpecularIters);

@@ -311,6 +311,22 @@ class BVH:
                                  C.byref(st)))
         return rgb, st.as_dict()
 
+    def trace_nee(self, origins, directions, depth: int, samples: int = 1, seed: int = PT_SEED, states=None):
+        """The light-sampling estimator (include/pt_hip.h: next-event estimation, the same expected
+        value as trace() at every depth) along a batch of rays on the host (pt_bvh_trace_nee; no
+        device needed), bit-identical to Renderer.trace_nee. Arguments and result as trace(); the
+        stats also count shadow_rays and light_draws (rays = path and shadow segments together)."""
+        ref = _SceneRef(self)
+        o, d = _rays(origins, directions)
+        n = o.shape[0]
+        st_arr = _states(states, n, samples)
+        prm = _lib.pt_trace_params(depth, samples, seed, st_arr.ctypes.data if st_arr is not None else None)
+        rgb = np.empty((n, 3), dtype=np.float32)
+        st = _lib.pt_nee_stats()
+        check(lib().pt_bvh_trace_nee(C.byref(ref.s), o.ctypes.data, d.ctypes.data, n, C.byref(prm), rgb.ctypes.data,
+                                     C.byref(st)))
+        return rgb, st.as_dict()
+
     def trace_grad(self, origins, directions, grad_rgb, depth: int, samples: int = 1, seed: int = PT_SEED, states=None,
                    color=None, emit=None, want=GRAD_WANT):
         """Renderer.trace_grad on the host (pt_bvh_trace_grad; no device needed): the same
@@ -379,6 +395,19 @@ def scene_info(bvh: BVH) -> dict:
     info = np.zeros(len(SCENE_INFO_KEYS), dtype=np.int32)
     check(lib().pt_scene_info(C.byref(ref.s), info.ctypes.data, len(info)))
     return dict(zip(SCENE_INFO_KEYS, info.tolist()))
+
+
+def scene_lights(bvh: BVH) -> dict:
+    """The light table of `bvh` as the light-sampling estimator reads it (pt_scene_lights; no device
+    needed): {"tri": the lights' indices into `triangles` (int32), "cdf": the running float32 sum
+    of their areas, "area": its last entry (0.0 without lights)}."""
+    ref = _SceneRef(bvh)
+    n = len(bvh.triangles)
+    tri = np.empty(n, dtype=np.int32)
+    cdf = np.empty(n, dtype=np.float32)
+    count, area = C.c_int64(0), C.c_float(0.0)
+    check(lib().pt_scene_lights(C.byref(ref.s), tri.ctypes.data, cdf.ctypes.data, n, C.byref(count), C.byref(area)))
+    return {"tri": tri[:count.value].copy(), "cdf": cdf[:count.value].copy(), "area": np.float32(area.value)}
 
 
 class Renderer:
@@ -702,6 +731,55 @@ class Renderer:
         rgb = np.empty((n, 3), dtype=np.float32)
         check(lib().pt_ctx_trace(self.h, o.ctypes.data, d.ctypes.data, n, C.byref(prm), rgb.ctypes.data, 0, C.byref(st)))
         return rgb, st.as_dict()
+
+    def trace_nee(self, origins, directions, depth: int, samples: int = 1, seed: int = PT_SEED, states=None, out=None):
+        """The light-sampling estimator (include/pt_hip.h) along a batch of the caller's rays on
+        this context's scene (pt_ctx_trace_nee): arguments, numpy and tensor paths as trace(),
+        bit-identical to BVH.trace_nee. Tensors follow the rule of the device-pointer paths: on
+        the context's device, and torch's current stream is waited for before they are read."""
+        st = _lib.pt_nee_stats()
+        if _is_tensor(origins):
+            n = origins.numel() // 3
+            if out is None:
+                import torch
+                out = torch.empty((n, 3), dtype=torch.float32, device=origins.device)
+            tens = [origins, directions, out] + ([states] if states is not None else [])
+            for x in tens:
+                if not _is_tensor(x) or not x.is_contiguous() or not x.is_cuda or x.element_size() != 4:
+                    raise ValueError("tensors must be contiguous 32-bit tensors on the context's device")
+            if directions.numel() != 3 * n or out.numel() != 3 * n or (states is not None and states.numel() != n * samples):
+                raise ValueError("directions and out must hold n x 3 elements, states n x samples")
+            _own_device_tensors(self.device, *tens)
+            prm = _lib.pt_trace_params(depth, samples, seed, states.data_ptr() if states is not None else None)
+            check(lib().pt_ctx_trace_nee(self.h, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()), n,
+                                         C.byref(prm), C.c_void_p(out.data_ptr()), 1, C.byref(st)))
+            return out, st.as_dict()
+        o, d = _rays(origins, directions)
+        n = o.shape[0]
+        st_arr = _states(states, n, samples)
+        prm = _lib.pt_trace_params(depth, samples, seed, st_arr.ctypes.data if st_arr is not None else None)
+        rgb = np.empty((n, 3), dtype=np.float32)
+        check(lib().pt_ctx_trace_nee(self.h, o.ctypes.data, d.ctypes.data, n, C.byref(prm), rgb.ctypes.data, 0, C.byref(st)))
+        return rgb, st.as_dict()
+
+    def render_nee(self, camera: Camera, samples: int, depth: int, seed: int = PT_SEED, part_index: int = 0,
+                   part_count: int = 1, band_rows: int = 1, out=None, want: Sequence[str] = ()):
+        """Render this part's rows with the light-sampling estimator (pt_ctx_render_nee) along the
+        render's own camera rays: (img, moments, stats). img is the float32 sum of `samples`
+        samples per pixel in sample order, divided by `samples`; moments holds the entries of
+        `want` ("sum", "sumsq", "sem", as render_moments defines them) over those samples. One
+        shot: it cannot be continued, and it ends this context's running sum. `out`: None (numpy
+        results) or a torch float32 tensor on this context's device, written in place; the moments
+        are then tensors there."""
+        W, H = camera.res
+        rows = self.part_rows(H, part_index, part_count, band_rows)
+        prm = _lib.pt_params(samples, depth, seed, part_index, part_count, band_rows, 0, 0)
+        img, res, img_ptr, mom, dev = self._moments_io(rows, W, want, out)
+        if dev:
+            _own_device_tensors(self.device, out)
+        st = _lib.pt_nee_stats()
+        check(lib().pt_ctx_render_nee(self.h, C.byref(camera.c), C.byref(prm), img_ptr, C.byref(mom), dev, C.byref(st)))
+        return img, res, st.as_dict()
 
     def trace_grad(self, origins, directions, grad_rgb, depth: int, samples: int = 1, seed: int = PT_SEED, states=None,
                    color=None, emit=None, want=GRAD_WANT):

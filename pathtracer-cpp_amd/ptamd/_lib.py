@@ -36,6 +36,7 @@ EXPORTED = (
     "pt_ctx_render_adaptive",
     "pt_moments_variance", "pt_ctx_moments_variance", "pt_image_denoise", "pt_ctx_denoise", "pt_ctx_render_denoised",
     "pt_image_temporal", "pt_ctx_temporal", "pt_ctx_render_temporal",
+    "pt_scene_lights", "pt_bvh_trace_nee", "pt_ctx_trace_nee", "pt_ctx_render_nee",
 )
 PT_MAX_DEVICES = 16
 
@@ -126,6 +127,17 @@ class pt_grad_stats(C.Structure):
     def as_dict(self) -> dict:
         d = self.trace.as_dict()
         d.update(terms=self.terms, grad_ms=self.grad_ms, lds_table=self.lds_table)
+        return d
+
+
+class pt_nee_stats(C.Structure):
+    """Light sampling (include/pt_hip.h): pt_trace_stats (rays = path and shadow segments) and the light counts."""
+    _fields_ = [("trace", pt_trace_stats), ("shadow_rays", C.c_uint64), ("light_draws", C.c_uint64),
+                ("lights", C.c_int32), ("light_area", C.c_float)]
+
+    def as_dict(self) -> dict:
+        d = self.trace.as_dict()
+        d.update(shadow_rays=self.shadow_rays, light_draws=self.light_draws, lights=self.lights, light_area=self.light_area)
         return d
 
 
@@ -239,6 +251,7 @@ class pt_aov(C.Structure):
 
 
 assert C.sizeof(pt_bvh_node) == 40 and C.sizeof(pt_material) == 32 and C.sizeof(pt_trace_stats) == 64
+assert C.sizeof(pt_nee_stats) == 88
 assert C.sizeof(pt_denoise_params) == 20 and C.sizeof(pt_denoise_stats) == 96 and C.sizeof(pt_denoise_guides) == 40
 assert C.sizeof(pt_temporal_params) == 16 and C.sizeof(pt_temporal_stats) == 24 and C.sizeof(pt_temporal_history) == 56
 
@@ -371,6 +384,14 @@ def lib() -> C.CDLL:
             L.pt_ctx_render_temporal.argtypes = [P, C.POINTER(pt_camera), C.POINTER(pt_params),
                                                  C.POINTER(pt_temporal_params), C.POINTER(pt_denoise_params), C.c_int,
                                                  P, P, C.c_int, C.POINTER(pt_render_temporal_stats)]
+        if hasattr(L, "pt_ctx_trace_nee"):  # absent from older builds used in A/B runs
+            L.pt_scene_lights.argtypes = [C.POINTER(pt_scene), P, P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_float)]
+            L.pt_bvh_trace_nee.argtypes = [C.POINTER(pt_scene), P, P, C.c_int64, C.POINTER(pt_trace_params), P,
+                                           C.POINTER(pt_nee_stats)]
+            L.pt_ctx_trace_nee.argtypes = [P, P, P, C.c_int64, C.POINTER(pt_trace_params), P, C.c_int,
+                                           C.POINTER(pt_nee_stats)]
+            L.pt_ctx_render_nee.argtypes = [P, C.POINTER(pt_camera), C.POINTER(pt_params), P, C.POINTER(pt_moments),
+                                            C.c_int, C.POINTER(pt_nee_stats)]
         if hasattr(L, "pt_debug_rccl_failover"):  # test hooks (absent from older builds used in A/B runs)
             L.pt_debug_rccl_failover.argtypes = [C.c_int32, C.c_int32, P]
         if hasattr(L, "pt_debug_rtc_cache"):
