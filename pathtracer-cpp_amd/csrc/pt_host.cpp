@@ -1204,10 +1204,7 @@ int pt_bvh_trace(const pt_scene* scene, const float* origins, const float* dirs,
     if (stats) memset(stats, 0, sizeof(*stats));
     if (!prm) return set_error(PT_E_ARG, "pt_bvh_trace: params is NULL");
     if (n < 0) return set_error(PT_E_ARG, "pt_bvh_trace: n = %lld is negative", (long long)n);
-    if (prm->depth < 0 || prm->depth > PT_MAX_DEPTH)
-        return set_error(PT_E_ARG, "pt_bvh_trace: depth %d outside 0..%d", prm->depth, PT_MAX_DEPTH);
-    if (prm->spp < 1 || prm->spp > kTraceMaxSpp)
-        return set_error(PT_E_ARG, "pt_bvh_trace: spp %d outside 1..%d", prm->spp, kTraceMaxSpp);
+    if (int prc = trace_params_check("pt_bvh_trace", prm)) return prc;
     PackedScene ps;
     const int rc = pack_scene(scene, ps);  // pt_scene_validate's checks: the walk cannot leave the arrays
     if (rc) return rc;
@@ -1313,10 +1310,7 @@ int pt_bvh_trace_nee(const pt_scene* scene, const float* origins, const float* d
     if (stats) memset(stats, 0, sizeof(*stats));
     if (!prm) return set_error(PT_E_ARG, "pt_bvh_trace_nee: params is NULL");
     if (n < 0) return set_error(PT_E_ARG, "pt_bvh_trace_nee: n = %lld is negative", (long long)n);
-    if (prm->depth < 0 || prm->depth > PT_MAX_DEPTH)
-        return set_error(PT_E_ARG, "pt_bvh_trace_nee: depth %d outside 0..%d", prm->depth, PT_MAX_DEPTH);
-    if (prm->spp < 1 || prm->spp > kTraceMaxSpp)
-        return set_error(PT_E_ARG, "pt_bvh_trace_nee: spp %d outside 1..%d", prm->spp, kTraceMaxSpp);
+    if (int prc = trace_params_check("pt_bvh_trace_nee", prm)) return prc;
     PackedScene ps;
     const int rc = pack_scene(scene, ps);  // pt_scene_validate's checks: the walk cannot leave the arrays
     if (rc) return rc;
@@ -1423,10 +1417,7 @@ int pt_bvh_trace_grad(const pt_scene* scene, const float* origins, const float* 
     if (!prm) return set_error(PT_E_ARG, "pt_bvh_trace_grad: params is NULL");
     if (!io) return set_error(PT_E_ARG, "pt_bvh_trace_grad: io is NULL");
     if (n < 0) return set_error(PT_E_ARG, "pt_bvh_trace_grad: n = %lld is negative", (long long)n);
-    if (prm->depth < 0 || prm->depth > PT_MAX_DEPTH)
-        return set_error(PT_E_ARG, "pt_bvh_trace_grad: depth %d outside 0..%d", prm->depth, PT_MAX_DEPTH);
-    if (prm->spp < 1 || prm->spp > kTraceMaxSpp)
-        return set_error(PT_E_ARG, "pt_bvh_trace_grad: spp %d outside 1..%d", prm->spp, kTraceMaxSpp);
+    if (int prc = trace_params_check("pt_bvh_trace_grad", prm)) return prc;
     PackedScene ps;
     const int rc = pack_scene(scene, ps);  // pt_scene_validate's checks: the walk cannot leave the arrays
     if (rc) return rc;

@@ -102,6 +102,14 @@ constexpr size_t kLdsGranule = 256;
 // ray's records always fit a launch (pt_ctx_trace cuts launches over rays only).
 constexpr int kSpecularIterBound = 1 << 16;
 constexpr int kTraceMaxSpp = 1 << 20;
+// The depth and spp ranges every entry point that traces caller-supplied rays checks (`who`: its name).
+inline int trace_params_check(const char* who, const pt_trace_params* prm) {
+    if (prm->depth < 0 || prm->depth > PT_MAX_DEPTH)
+        return set_error(PT_E_ARG, "%s: depth %d outside 0..%d", who, prm->depth, PT_MAX_DEPTH);
+    if (prm->spp < 1 || prm->spp > kTraceMaxSpp)
+        return set_error(PT_E_ARG, "%s: spp %d outside 1..%d", who, prm->spp, kTraceMaxSpp);
+    return PT_OK;
+}
 constexpr int kPairQueueMin = 256;  // shortest flat pair queue (entries per wave) the launch picks for occupancy
 
 struct PackedScene {

@@ -381,14 +381,14 @@ struct pt_ctx {
     size_t tbuf_floats = 0;
     float* d_tstates = nullptr;              // staging of a host-pointer call's LCG states (uint32)
     size_t tstates_words = 0;
-    unsigned long long* d_tctr = nullptr;    // work head, ray and runaway counters of a call (4 x u64)
+    unsigned long long* d_tctr = nullptr;    // counters of a call (6 x u64): work head, rays, gradient terms, runaway,
+                                             // shadow segments, light draws (trace_counters)
     // light sampling (pt_ctx_trace_nee, pt_ctx_render_nee; pt_nee.hip): the scene's light table, made on the
     // host when the scene is set and uploaded by the first call that samples lights; pt_ctx_trace's staging
     LightTable lights;
     bool lights_uploaded = false;
     uint8_t* d_lights = nullptr;             // [geom 5 x float4][cdf][tri][listed per caller triangle]
     size_t lights_bytes = 0;
-    unsigned long long* d_nctr = nullptr;    // d_tctr's four counters, then shadow segments and light draws
     // material gradients (pt_ctx_trace_grad): pt_ctx_trace's buffers, and
     double* d_gtab = nullptr;                // the gradient table, 6 doubles per caller triangle, then the split outputs
     size_t gtab_doubles = 0;
@@ -1107,6 +1107,13 @@ int kernel_path_of(const pt_ctx* c, const RenderPlan& P) {
                                     : PT_PATH_TREE_GLOBAL;
 }
 
+// What a call that counted runaway specular rejection loops returns.
+int runaway_result(unsigned long long loops) {
+    if (loops != 0)
+        return set_error(PT_E_RUNAWAY, "%llu specular rejection loops hit the %d-iteration bound", loops, kMaxSpecularIters);
+    return PT_OK;
+}
+
 // Progress reports, the image and the counters back, the stats and pt_debug_ctx_plan's record.
 int finish_render(pt_ctx* c, const RenderPlan& P, const TraceArgs& A, const pt_params* prm, const RenderEvents& E,
                   const LaunchLog& log, float* out, const float* dst, bool out_is_device,
@@ -1166,10 +1173,7 @@ int finish_render(pt_ctx* c, const RenderPlan& P, const TraceArgs& A, const pt_p
         stats->kernel_path = kernel_path;
         stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     }
-    if (h_ctr[3] != 0)
-        return set_error(PT_E_RUNAWAY, "%llu specular rejection loops hit the %d-iteration bound", h_ctr[3],
-                         kMaxSpecularIters);
-    return PT_OK;
+    return runaway_result(h_ctr[3]);
 }
 
 // Samples [s_lo, s_hi) of this part added to the running sum (a new sum when s_lo == 0),
@@ -1266,11 +1270,11 @@ int moments_range(pt_ctx* c, const pt_camera* cam, const pt_params* prm, int32_t
     return rc;
 }
 
-// The context's moments to the caller's arrays (device or host pointers): S and Q are copies of
-// d_mom's halves, sem is computed from them with n = prog_spp, or with each pixel's own n
+// The context's moments over npix pixels to the caller's arrays (device or host pointers): S and Q
+// are copies of d_mom's halves, sem is computed from them with n = spp, or with each pixel's own n
 // (d_spp, after per-pixel rounds). Synchronous.
-int moments_export(pt_ctx* c, const pt_moments* mom, int is_device, const int32_t* d_spp = nullptr) {
-    const size_t nval = 3 * (size_t)c->prog_npix;
+int moments_export(pt_ctx* c, const pt_moments* mom, int is_device, int npix, int spp, const int32_t* d_spp = nullptr) {
+    const size_t nval = 3 * (size_t)npix;
     if (!mom || nval == 0) return PT_OK;
     const hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     if (mom->sum) HIP_TRY(hipMemcpyAsync(mom->sum, c->d_mom, nval * sizeof(double), kind, c->stream));
@@ -1283,7 +1287,8 @@ int moments_export(pt_ctx* c, const pt_moments* mom, int is_device, const int32_
             if (int rc = adaptive_sem(c->stream, c->d_mom, nval, d_spp, dst)) return rc;
         } else {
             hipLaunchKernelGGL(pt_moments_sem_kernel, dim3((unsigned)((nval + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                               c->stream, c->d_mom, nval, c->prog_spp, dst);
+                               c->stream, c->d_mom, nval, spp, dst);
+            HIP_TRY(hipGetLastError());
         }
         if (!is_device) HIP_TRY(hipMemcpyAsync(mom->sem, dst, nval * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     }
@@ -1419,7 +1424,7 @@ void pt_ctx_destroy(pt_ctx* c) {
                     (void*)c->d_accum, (void*)c->d_out, (void*)c->d_ctr, (void*)c->d_stamps, (void*)c->d_rgb8, (void*)c->d_thr, (void*)c->d_xstack,
                     (void*)c->d_rank_tri, (void*)c->d_qstack, (void*)c->d_qbuf, (void*)c->d_qhits,
                     (void*)c->d_tslab, (void*)c->d_trec, (void*)c->d_tbuf, (void*)c->d_tstates, (void*)c->d_tctr,
-                    (void*)c->d_lights, (void*)c->d_nctr,
+                    (void*)c->d_lights,
                     (void*)c->d_gtab, (void*)c->d_gmats, (void*)c->d_gbuf, (void*)c->d_mom, (void*)c->d_mcount, (void*)c->d_sem,
                     (void*)c->d_alist[0], (void*)c->d_alist[1], (void*)c->d_aspp, (void*)c->d_aslab, (void*)c->d_arec, (void*)c->d_actr})
         if (p) (void)hipFree(p);
@@ -1579,7 +1584,7 @@ int pt_ctx_render_moments(pt_ctx* c, const pt_camera* cam, const pt_params* prm,
                           float* out, const pt_moments* mom, int out_is_device, pt_stats* stats) {
     const int rc = moments_range(c, cam, prm, s_first, s_count, out, out_is_device, stats);
     if (rc && rc != PT_E_RUNAWAY) return rc;
-    if (int xrc = moments_export(c, mom, out_is_device)) return xrc;
+    if (int xrc = moments_export(c, mom, out_is_device, c->prog_npix, c->prog_spp)) return xrc;
     return rc;
 }
 
@@ -1622,7 +1627,7 @@ int pt_ctx_render_converge(pt_ctx* c, const pt_camera* cam, const pt_params* prm
         HIP_TRY(hipMemcpyAsync(out, c->d_out, 3 * (size_t)c->prog_npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
-    if (int xrc = moments_export(c, mom, out_is_device)) return xrc;
+    if (int xrc = moments_export(c, mom, out_is_device, c->prog_npix, c->prog_spp)) return xrc;
     S.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     if (cs) *cs = S;
     if (runaway)
@@ -1661,6 +1666,11 @@ int query_buffers(pt_ctx* c, const WalkPlan& plan) {
 
 struct EventPair {
     hipEvent_t a = nullptr, b = nullptr;
+    int create() {
+        HIP_TRY(hipEventCreate(&a));
+        HIP_TRY(hipEventCreate(&b));
+        return PT_OK;
+    }
     ~EventPair() {
         if (a) (void)hipEventDestroy(a);
         if (b) (void)hipEventDestroy(b);
@@ -1719,8 +1729,7 @@ int pt_ctx_intersect(pt_ctx* c, const float* origins, const float* dirs, int64_t
         s_out = reinterpret_cast<int32_t*>(s_t + chunk);
     }
     EventPair ev;
-    HIP_TRY(hipEventCreate(&ev.a));
-    HIP_TRY(hipEventCreate(&ev.b));
+    if ((rc = ev.create())) return rc;
     double kernel_ms = 0;
     int launches = 0;
     for (int64_t i0 = 0; i0 < n; i0 += chunk) {
@@ -1794,8 +1803,7 @@ int pt_ctx_render_aov(pt_ctx* c, const pt_camera* cam, const pt_params* prm, int
     }
     const pt_aov d_out{dev[0], reinterpret_cast<int32_t*>(dev[1]), dev[2], dev[3], dev[4], dev[5]};
     EventPair ev;
-    HIP_TRY(hipEventCreate(&ev.a));
-    HIP_TRY(hipEventCreate(&ev.b));
+    if ((rc = ev.create())) return rc;
     HIP_TRY(hipEventRecord(ev.a, c->stream));
     if ((rc = aov_launch(c->stream, sc, plan, cam, prm, shape, sample, &d_out, c->d_qstack, c->d_qhits, query_force_exact())))
         return rc;
@@ -1811,151 +1819,255 @@ int pt_ctx_render_aov(pt_ctx* c, const pt_camera* cam, const pt_params* prm, int
     return query_finish(c, plan, (uint64_t)npix, ms, 1, t_start, stats);
 }
 
-// trace() (render.h:36-61) along the caller's rays: pt_paths_kernel fills a dense slab
-// [sample][ray][rgb] of one launch, pt_accumulate_kernel adds a ray's samples in order and
-// divides. Launches are cut over rays only: m rays with m * spp < 2^31 records inside the slab
-// budget (PT_TRACE_CHUNK, test hook: rays per launch).
-int pt_ctx_trace(pt_ctx* c, const float* origins, const float* dirs, int64_t n, const pt_trace_params* prm,
-                 float* rgb_out, int is_device, pt_trace_stats* stats) {
-    const auto t_start = std::chrono::steady_clock::now();
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!c) return set_error(PT_E_ARG, "pt_ctx_trace: context is NULL");
-    if (!prm) return set_error(PT_E_ARG, "pt_ctx_trace: params is NULL");
-    if (n < 0) return set_error(PT_E_ARG, "pt_ctx_trace: n = %lld is negative", (long long)n);
-    if (prm->depth < 0 || prm->depth > PT_MAX_DEPTH)
-        return set_error(PT_E_ARG, "pt_ctx_trace: depth %d outside 0..%d", prm->depth, PT_MAX_DEPTH);
-    if (prm->spp < 1 || prm->spp > kTraceMaxSpp)
-        return set_error(PT_E_ARG, "pt_ctx_trace: spp %d outside 1..%d", prm->spp, kTraceMaxSpp);
-    if (!c->have_scene) return set_error(PT_E_ARG, "pt_ctx_trace: no scene set");
-    if (n == 0) return PT_OK;
-    if (!origins || !dirs || !rgb_out) return set_error(PT_E_ARG, "pt_ctx_trace: NULL argument");
-    if (int rc0 = ctx_ready(c)) return rc0;
-    HIP_TRY(hipSetDevice(c->device));
-    const int64_t spp = prm->spp;
-    auto finish = [&](const WalkPlan* plan, const unsigned long long* ctr, double kms, double rms, int launches) {
-        if (!stats) return;
-        stats->rays = ctr[1];
-        stats->paths = (uint64_t)n * (uint64_t)spp;
-        stats->runaway = ctr[3];
-        stats->kernel_ms = kms;
-        stats->reduce_ms = rms;
-        stats->launches = launches;
-        if (plan) {
-            stats->lds_scene = plan->lds_scene;
-            stats->lds_stack = plan->lds_stack;
-            stats->lds_records = plan->lds_rec;
-        }
-        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-    };
-    if (prm->depth == 0) {  // trace() returns 0 (render.h:37): no ray is traced
-        if (is_device) {
-            HIP_TRY(hipMemsetAsync(rgb_out, 0, 3 * sizeof(float) * (size_t)n, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-        } else {
-            memset(rgb_out, 0, 3 * sizeof(float) * (size_t)n);
-        }
-        const unsigned long long zero[4] = {0, 0, 0, 0};
-        finish(nullptr, zero, 0, 0, 0);
+}  // extern "C"
+
+// ---------------------------------------------------------------- trace() along caller-supplied rays
+// pt_ctx_trace, pt_ctx_trace_nee and pt_ctx_trace_grad are one host loop (caller_rays_*) around
+// three kernels: the kernel fills a dense slab [sample][ray][rgb] of one launch,
+// pt_accumulate_kernel adds a ray's samples in order and divides. Launches are cut over rays only.
+// The buffers are their own (d_tslab, d_trec, d_tbuf, d_tstates, d_tctr), never d_accum, so a
+// progressive sum stays valid across them.
+namespace {
+
+// Three events around a launch and the pass that sums its slab: kernel = [0, 1), reduce = [1, 2).
+struct LaunchTimer {
+    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+    ~LaunchTimer() {
+        for (hipEvent_t x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+    int create() {
+        for (hipEvent_t& x : e) HIP_TRY(hipEventCreate(&x));
         return PT_OK;
     }
-    // rays per launch
-    int64_t m_max = std::min<int64_t>(n, ((1ll << 31) - 1) / spp);
-    m_max = std::min<int64_t>(m_max, (int64_t)(batch_bytes_budget(c->device, false) / (3 * sizeof(float) * (size_t)spp)));
-    if (!is_device) m_max = std::min(m_max, kQueryHostChunk);
-    if (const char* tc = hook_env("PT_TRACE_CHUNK"))
-        if (*tc) m_max = std::min<int64_t>(m_max, strtoll(tc, nullptr, 10));
-    m_max = std::max<int64_t>(m_max, 1);
-    const QueryScene sc = query_scene(c);
-    WalkPlan plan;
-    int rc;
-    if ((rc = paths_plan(sc, c->lds_usable, c->num_cus, prm->depth, m_max * spp, plan))) return rc;
-    if (plan.stack_ints > 0 && (rc = ensure(&c->d_qstack, &c->qstack_ints, plan.stack_ints))) return rc;
-    if (plan.rec_words > 0 && (rc = ensure(&c->d_trec, &c->trec_words, 2 * plan.rec_words))) return rc;
-    if ((rc = ensure(&c->d_tslab, &c->tslab_floats, 3 * (size_t)(m_max * spp)))) return rc;
-    if (!c->d_tctr) HIP_TRY(hipMalloc((void**)&c->d_tctr, 4 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemsetAsync(c->d_tctr, 0, 4 * sizeof(unsigned long long), c->stream));
-    // host pointers: staging [origins 3][dirs 3][rgb 3] x m_max, and the states
-    float *s_org = nullptr, *s_dir = nullptr, *s_out = nullptr;
-    if (!is_device) {
-        if ((rc = ensure(&c->d_tbuf, &c->tbuf_floats, 9 * (size_t)m_max))) return rc;
-        s_org = c->d_tbuf;
-        s_dir = s_org + 3 * m_max;
-        s_out = s_dir + 3 * m_max;
-        if (prm->states && (rc = ensure(&c->d_tstates, &c->tstates_words, (size_t)(m_max * spp)))) return rc;
+    int mark(int i, hipStream_t stream) {
+        HIP_TRY(hipEventRecord(e[i], stream));
+        return PT_OK;
     }
-    PathsLaunch l{};
-    l.spp = (int32_t)spp;
-    l.depth = prm->depth;
-    l.seed = prm->seed;
-    l.slab = c->d_tslab;
-    l.ctr = c->d_tctr;
+    // once the stream is synchronised: the two durations added to the caller's sums
+    int add(double* kernel_ms, double* reduce_ms) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, e[0], e[1]));
+        *kernel_ms += ms;
+        HIP_TRY(hipEventElapsedTime(&ms, e[1], e[2]));
+        *reduce_ms += ms;
+        return PT_OK;
+    }
+};
+
+// A call's counters, zeroed: work head, rays, gradient terms (pt_grad.hip), runaway, shadow
+// segments and light draws (pt_nee.hip). A launch zeroes only the work head again.
+constexpr int kTraceCounters = 6;
+int trace_counters(pt_ctx* c) {
+    if (!c->d_tctr) HIP_TRY(hipMalloc((void**)&c->d_tctr, kTraceCounters * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(c->d_tctr, 0, kTraceCounters * sizeof(unsigned long long), c->stream));
+    return PT_OK;
+}
+
+// The fields of a PathsLaunch that no launch of a call changes (the rays, m, ray_base and, where
+// launches are cut over samples, spp are the launch's own). d_qstack must have its size by now.
+int paths_launch_base(pt_ctx* c, int32_t spp, int32_t depth, uint32_t seed, float* slab, unsigned long long* ctr,
+                      float* grec, int dark, PathsLaunch& l) {
+    l = PathsLaunch{};
+    l.spp = spp;
+    l.depth = depth;
+    l.seed = seed;
+    l.slab = slab;
+    l.ctr = ctr;
     l.gstack = c->d_qstack;
-    l.grec = plan.rec_words > 0 ? c->d_trec : nullptr;
-    l.dark = c->dark ? 1 : 0;
+    l.grec = grec;
+    l.dark = dark;
     l.force_exact = query_force_exact();
-    {
-        const float2* tab = nullptr;
-        if ((rc = theta_choice(c, &l.theta_lanes, &tab))) return rc;
-        l.theta_tab = tab;
+    const float2* tab = nullptr;
+    if (int rc = theta_choice(c, &l.theta_lanes, &tab)) return rc;
+    l.theta_tab = tab;
+    return PT_OK;
+}
+
+int zero_output(pt_ctx* c, void* p, size_t bytes, int is_device) {
+    if (!p || bytes == 0) return PT_OK;
+    if (is_device) HIP_TRY(hipMemsetAsync(p, 0, bytes, c->stream));
+    else memset(p, 0, bytes);
+    return PT_OK;
+}
+
+// plan: nullptr when nothing was launched; records: the kernel keeps path records.
+void fill_trace_stats(pt_trace_stats* ts, const WalkPlan* plan, bool records, const unsigned long long* ctr, uint64_t paths,
+                      double kernel_ms, double reduce_ms, int launches, std::chrono::steady_clock::time_point t_start) {
+    if (!ts) return;
+    ts->rays = ctr[1];
+    ts->paths = paths;
+    ts->runaway = ctr[3];
+    ts->kernel_ms = kernel_ms;
+    ts->reduce_ms = reduce_ms;
+    ts->launches = launches;
+    if (plan) {
+        ts->lds_scene = plan->lds_scene;
+        ts->lds_stack = plan->lds_stack;
+        if (records) ts->lds_records = plan->lds_rec;
     }
-    EventPair ev, ev2;
-    HIP_TRY(hipEventCreate(&ev.a));
-    HIP_TRY(hipEventCreate(&ev.b));
-    HIP_TRY(hipEventCreate(&ev2.a));
+    ts->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+}
+
+// One call along the caller's rays: what the entry point asks for, what caller_rays_begin derives
+// and what the launches leave behind.
+struct CallerRays {
+    const char* who;  // the entry point's name, for its messages
+    const float *origins, *dirs;
+    int64_t n;
+    const pt_trace_params* prm;
+    float* rgb_out;  // nullptr (pt_ctx_trace_grad without "rgb"): nothing is summed or copied
+    int is_device;
+    int dark;      // PathsLaunch::dark
+    bool records;  // the kernel keeps path records
+    std::chrono::steady_clock::time_point t_start;
+    // caller_rays_begin
+    int64_t m_max = 0;  // rays per launch; 0: no ray is traced
+    WalkPlan plan{};
+    PathsLaunch l{};
+    float *s_org = nullptr, *s_dir = nullptr, *s_out = nullptr;  // a host-pointer call's staging
+    // caller_rays_loop, caller_rays_end
+    unsigned long long ctr[kTraceCounters] = {};
     double kernel_ms = 0, reduce_ms = 0;
     int launches = 0;
+};
+
+// What every entry point checks first, in this order. null_extra: the name of an argument of its
+// own that is NULL (it comes after params), or nullptr.
+int caller_rays_check(const char* who, const pt_ctx* c, const pt_trace_params* prm, const char* null_extra, int64_t n) {
+    if (!c) return set_error(PT_E_ARG, "%s: context is NULL", who);
+    if (!prm) return set_error(PT_E_ARG, "%s: params is NULL", who);
+    if (null_extra) return set_error(PT_E_ARG, "%s: %s is NULL", who, null_extra);
+    if (n < 0) return set_error(PT_E_ARG, "%s: n = %lld is negative", who, (long long)n);
+    if (int rc = trace_params_check(who, prm)) return rc;
+    if (!c->have_scene) return set_error(PT_E_ARG, "%s: no scene set", who);
+    return PT_OK;
+}
+
+// The last check (a NULL array), then the context's stream and device.
+int caller_rays_ready(const char* who, pt_ctx* c, bool null_array) {
+    if (null_array) return set_error(PT_E_ARG, "%s: NULL argument", who);
+    if (int rc = ctx_ready(c)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    return PT_OK;
+}
+
+// Without a ray to trace (n or depth 0) the answer, rgb +0 (render.h:37), and m_max = 0. Else the
+// rays per launch, the plan (plan_for(items, WalkPlan&) for m_max x spp items), the buffers, the
+// zeroed counters and the launch's fixed fields.
+template <class Plan>
+int caller_rays_begin(pt_ctx* c, CallerRays& R, Plan&& plan_for) {
+    const int64_t n = R.n, spp = R.prm->spp;
+    int rc;
+    if (n == 0 || R.prm->depth == 0) {
+        if ((rc = zero_output(c, R.rgb_out, 3 * sizeof(float) * (size_t)n, R.is_device))) return rc;
+        if (R.is_device) HIP_TRY(hipStreamSynchronize(c->stream));
+        return PT_OK;
+    }
+    // rays per launch: m * spp < 2^31 records inside the slab budget, a host-pointer call's staging
+    // (PT_TRACE_CHUNK, test hook: rays per launch)
+    int64_t m_max = std::min<int64_t>(n, ((1ll << 31) - 1) / spp);
+    m_max = std::min<int64_t>(m_max, (int64_t)(batch_bytes_budget(c->device, false) / (3 * sizeof(float) * (size_t)spp)));
+    if (!R.is_device) m_max = std::min(m_max, kQueryHostChunk);
+    if (const char* tc = hook_env("PT_TRACE_CHUNK"))
+        if (*tc) m_max = std::min<int64_t>(m_max, strtoll(tc, nullptr, 10));
+    R.m_max = m_max = std::max<int64_t>(m_max, 1);
+    if ((rc = plan_for(m_max * spp, R.plan))) return rc;
+    if (R.plan.stack_ints > 0 && (rc = ensure(&c->d_qstack, &c->qstack_ints, R.plan.stack_ints))) return rc;
+    if (R.plan.rec_words > 0 && (rc = ensure(&c->d_trec, &c->trec_words, 2 * R.plan.rec_words))) return rc;
+    if ((rc = ensure(&c->d_tslab, &c->tslab_floats, 3 * (size_t)(m_max * spp)))) return rc;
+    if ((rc = trace_counters(c))) return rc;
+    // host pointers: staging [origins 3][dirs 3][rgb 3] x m_max, and the states
+    if (!R.is_device) {
+        if ((rc = ensure(&c->d_tbuf, &c->tbuf_floats, 9 * (size_t)m_max))) return rc;
+        R.s_org = c->d_tbuf;
+        R.s_dir = R.s_org + 3 * m_max;
+        R.s_out = R.s_dir + 3 * m_max;
+        if (R.prm->states && (rc = ensure(&c->d_tstates, &c->tstates_words, (size_t)(m_max * spp)))) return rc;
+    }
+    return paths_launch_base(c, (int32_t)spp, R.prm->depth, R.prm->seed, c->d_tslab, c->d_tctr,
+                             R.plan.rec_words > 0 ? c->d_trec : nullptr, R.dark, R.l);
+}
+
+// The launches, m_max rays each: stage (host pointers; then stage(i0, m), the entry point's own
+// staging), zero the work head, launch(PathsLaunch), the in-order sum, copy back, synchronise.
+template <class Launch, class Stage>
+int caller_rays_loop(pt_ctx* c, CallerRays& R, Launch&& launch, Stage&& stage) {
+    if (R.m_max == 0) return PT_OK;
+    const int64_t n = R.n, spp = R.prm->spp, m_max = R.m_max;
+    const uint32_t* states = R.prm->states;
+    PathsLaunch& l = R.l;
+    LaunchTimer timer;
+    int rc;
+    if ((rc = timer.create())) return rc;
     for (int64_t i0 = 0; i0 < n; i0 += m_max) {
         const int32_t m = (int32_t)std::min(m_max, n - i0);
         l.m = m;
         l.ray_base = (uint32_t)i0;
-        l.org = origins + 3 * i0;
-        l.dir = dirs + 3 * i0;
-        l.states = prm->states ? prm->states + i0 * spp : nullptr;
-        float* k_out = rgb_out + 3 * i0;
-        if (!is_device) {
-            HIP_TRY(hipMemcpyAsync(s_org, l.org, 3 * sizeof(float) * (size_t)m, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(s_dir, l.dir, 3 * sizeof(float) * (size_t)m, hipMemcpyHostToDevice, c->stream));
-            if (prm->states) {
+        l.org = R.origins + 3 * i0;
+        l.dir = R.dirs + 3 * i0;
+        l.states = states ? states + i0 * spp : nullptr;
+        float* k_out = R.rgb_out ? R.rgb_out + 3 * i0 : nullptr;
+        if (!R.is_device) {
+            HIP_TRY(hipMemcpyAsync(R.s_org, l.org, 3 * sizeof(float) * (size_t)m, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(R.s_dir, l.dir, 3 * sizeof(float) * (size_t)m, hipMemcpyHostToDevice, c->stream));
+            if (states) {
                 HIP_TRY(hipMemcpyAsync(c->d_tstates, l.states, sizeof(uint32_t) * (size_t)(m * spp), hipMemcpyHostToDevice,
                                        c->stream));
                 l.states = reinterpret_cast<const uint32_t*>(c->d_tstates);
             }
-            l.org = s_org;
-            l.dir = s_dir;
-            k_out = s_out;
+            l.org = R.s_org;
+            l.dir = R.s_dir;
+            k_out = R.rgb_out ? R.s_out : nullptr;
         }
+        if ((rc = stage(i0, m))) return rc;
         HIP_TRY(hipMemsetAsync(c->d_tctr, 0, sizeof(unsigned long long), c->stream));  // work head only
-        HIP_TRY(hipEventRecord(ev.a, c->stream));
-        if ((rc = paths_launch(c->stream, sc, plan, l))) return rc;
-        HIP_TRY(hipEventRecord(ev.b, c->stream));
-        // the ray's samples in order from +0, then / spp (image.h:27-31, 37-40)
-        hipLaunchKernelGGL(pt_accumulate_kernel, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->d_tslab,
-                           (float*)nullptr, k_out, (int)m, (int)spp, 1, 1, 0, (float)spp, (const uint32_t*)nullptr, 0);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(ev2.a, c->stream));
-        launches++;
-        if (!is_device)
-            HIP_TRY(hipMemcpyAsync(rgb_out + 3 * i0, s_out, 3 * sizeof(float) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = timer.mark(0, c->stream))) return rc;
+        if ((rc = launch(l))) return rc;
+        if ((rc = timer.mark(1, c->stream))) return rc;
+        if (k_out) {  // the ray's samples in order from +0, then / spp (image.h:27-31, 37-40)
+            hipLaunchKernelGGL(pt_accumulate_kernel, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->d_tslab,
+                               (float*)nullptr, k_out, (int)m, (int)spp, 1, 1, 0, (float)spp, (const uint32_t*)nullptr, 0);
+            HIP_TRY(hipGetLastError());
+        }
+        if ((rc = timer.mark(2, c->stream))) return rc;
+        R.launches++;
+        if (!R.is_device && R.rgb_out)
+            HIP_TRY(hipMemcpyAsync(R.rgb_out + 3 * i0, R.s_out, 3 * sizeof(float) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
-        kernel_ms += ms;
-        HIP_TRY(hipEventElapsedTime(&ms, ev.b, ev2.a));
-        reduce_ms += ms;
+        if ((rc = timer.add(&R.kernel_ms, &R.reduce_ms))) return rc;
     }
-    unsigned long long h_ctr[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h_ctr, c->d_tctr, sizeof(h_ctr), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    finish(&plan, h_ctr, kernel_ms, reduce_ms, launches);
-    if (h_ctr[3] != 0)
-        return set_error(PT_E_RUNAWAY, "%llu specular rejection loops hit the %d-iteration bound", h_ctr[3],
-                         kMaxSpecularIters);
     return PT_OK;
+}
+
+// The counters back (synchronises; also what the entry point queued after the launches).
+int caller_rays_end(pt_ctx* c, CallerRays& R) {
+    if (R.m_max == 0) return PT_OK;
+    HIP_TRY(hipMemcpyAsync(R.ctr, c->d_tctr, sizeof(R.ctr), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+// The call's pt_trace_stats (ts may be NULL), and what the call returns: PT_OK or PT_E_RUNAWAY.
+int caller_rays_stats(const CallerRays& R, pt_trace_stats* ts) {
+    fill_trace_stats(ts, R.m_max ? &R.plan : nullptr, R.records, R.ctr, (uint64_t)R.n * (uint64_t)R.prm->spp, R.kernel_ms,
+                     R.reduce_ms, R.launches, R.t_start);
+    return runaway_result(R.ctr[3]);
+}
+
+// An entry point without steps of its own between those four.
+template <class Plan, class Launch>
+int caller_rays(pt_ctx* c, CallerRays& R, pt_trace_stats* ts, Plan&& plan_for, Launch&& launch) {
+    int rc;
+    if ((rc = caller_rays_begin(c, R, plan_for))) return rc;
+    if ((rc = caller_rays_loop(c, R, launch, [](int64_t, int32_t) { return PT_OK; }))) return rc;
+    if ((rc = caller_rays_end(c, R))) return rc;
+    return caller_rays_stats(R, ts);
 }
 
 // ---- light sampling (pt_nee.hip)
 // The context's light table on its device: uploaded by the first call after pt_ctx_set_scene.
-static int nee_lights(pt_ctx* c, NeeLights* out) {
+int nee_lights(pt_ctx* c, NeeLights* out) {
     const LightTable& lt = c->lights;
     const size_t nl = lt.tri.size();
     *out = NeeLights{nullptr, nullptr, nullptr, nullptr, 0, 0.0f, 0.0f};
@@ -1981,157 +2093,56 @@ static int nee_lights(pt_ctx* c, NeeLights* out) {
     return PT_OK;
 }
 
-// What both entry points launch with: the plan's global stack, the six zeroed counters, and the
-// fields of a launch that do not change from one launch to the next.
-static int nee_setup(pt_ctx* c, const WalkPlan& plan, int32_t spp, int32_t depth, uint32_t seed, PathsLaunch& l) {
-    int rc;
-    if (plan.stack_ints > 0 && (rc = ensure(&c->d_qstack, &c->qstack_ints, plan.stack_ints))) return rc;
-    if (!c->d_nctr) HIP_TRY(hipMalloc((void**)&c->d_nctr, 6 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemsetAsync(c->d_nctr, 0, 6 * sizeof(unsigned long long), c->stream));
-    l = PathsLaunch{};
-    l.spp = spp;
-    l.depth = depth;
-    l.seed = seed;
-    l.slab = c->d_tslab;
-    l.ctr = c->d_nctr;
-    l.gstack = c->d_qstack;
-    l.grec = nullptr;
-    l.dark = 0;
-    l.force_exact = query_force_exact();
-    const float2* tab = nullptr;
-    if ((rc = theta_choice(c, &l.theta_lanes, &tab))) return rc;
-    l.theta_tab = tab;
-    return PT_OK;
-}
-
-static void nee_stats(pt_nee_stats* stats, const pt_ctx* c, const WalkPlan* plan, const unsigned long long* ctr, uint64_t paths,
-                      double kms, double rms, int launches, std::chrono::steady_clock::time_point t_start) {
-    if (!stats) return;
-    stats->trace.rays = ctr[1];
-    stats->trace.paths = paths;
-    stats->trace.runaway = ctr[3];
-    stats->trace.kernel_ms = kms;
-    stats->trace.reduce_ms = rms;
-    stats->trace.launches = launches;
-    if (plan) {
-        stats->trace.lds_scene = plan->lds_scene;
-        stats->trace.lds_stack = plan->lds_stack;
-    }
-    stats->trace.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+void nee_light_stats(pt_nee_stats* stats, const pt_ctx* c, const unsigned long long* ctr) {
     stats->shadow_rays = ctr[4];
     stats->light_draws = ctr[5];
     stats->lights = (int32_t)c->lights.tri.size();
     stats->light_area = c->lights.area;
 }
 
-// pt_ctx_trace with pt_nee_kernel in place of pt_paths_kernel: the same cuts over rays
-// (PT_TRACE_CHUNK, test hook: rays per launch), staging and in-order sum; the counters are its own.
+}  // namespace
+
+extern "C" {
+
+// trace() (render.h:36-61) along the caller's rays: pt_paths_kernel under the shared loop.
+int pt_ctx_trace(pt_ctx* c, const float* origins, const float* dirs, int64_t n, const pt_trace_params* prm,
+                 float* rgb_out, int is_device, pt_trace_stats* stats) {
+    const auto t_start = std::chrono::steady_clock::now();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    static const char who[] = "pt_ctx_trace";
+    if (int rc = caller_rays_check(who, c, prm, nullptr, n)) return rc;
+    if (n == 0) return PT_OK;
+    if (int rc = caller_rays_ready(who, c, !origins || !dirs || !rgb_out)) return rc;
+    const QueryScene sc = query_scene(c);
+    CallerRays R{who, origins, dirs, n, prm, rgb_out, is_device, c->dark ? 1 : 0, true, t_start};
+    return caller_rays(
+        c, R, stats,
+        [&](int64_t items, WalkPlan& plan) { return paths_plan(sc, c->lds_usable, c->num_cus, prm->depth, items, plan); },
+        [&](const PathsLaunch& l) { return paths_launch(c->stream, sc, R.plan, l); });
+}
+
+// The light-sampling estimator along the caller's rays: pt_nee_kernel under the shared loop (no
+// path records; the stats add its own counters).
 int pt_ctx_trace_nee(pt_ctx* c, const float* origins, const float* dirs, int64_t n, const pt_trace_params* prm,
                      float* rgb_out, int is_device, pt_nee_stats* stats) {
     const auto t_start = std::chrono::steady_clock::now();
     if (stats) memset(stats, 0, sizeof(*stats));
-    if (!c) return set_error(PT_E_ARG, "pt_ctx_trace_nee: context is NULL");
-    if (!prm) return set_error(PT_E_ARG, "pt_ctx_trace_nee: params is NULL");
-    if (n < 0) return set_error(PT_E_ARG, "pt_ctx_trace_nee: n = %lld is negative", (long long)n);
-    if (prm->depth < 0 || prm->depth > PT_MAX_DEPTH)
-        return set_error(PT_E_ARG, "pt_ctx_trace_nee: depth %d outside 0..%d", prm->depth, PT_MAX_DEPTH);
-    if (prm->spp < 1 || prm->spp > kTraceMaxSpp)
-        return set_error(PT_E_ARG, "pt_ctx_trace_nee: spp %d outside 1..%d", prm->spp, kTraceMaxSpp);
-    if (!c->have_scene) return set_error(PT_E_ARG, "pt_ctx_trace_nee: no scene set");
+    static const char who[] = "pt_ctx_trace_nee";
+    if (int rc = caller_rays_check(who, c, prm, nullptr, n)) return rc;
     if (n == 0) return PT_OK;
-    if (!origins || !dirs || !rgb_out) return set_error(PT_E_ARG, "pt_ctx_trace_nee: NULL argument");
-    if (int rc0 = ctx_ready(c)) return rc0;
-    HIP_TRY(hipSetDevice(c->device));
-    const int64_t spp = prm->spp;
-    if (prm->depth == 0) {  // no segment is walked: every path returns +0
-        if (is_device) {
-            HIP_TRY(hipMemsetAsync(rgb_out, 0, 3 * sizeof(float) * (size_t)n, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-        } else {
-            memset(rgb_out, 0, 3 * sizeof(float) * (size_t)n);
-        }
-        const unsigned long long zero[6] = {0, 0, 0, 0, 0, 0};
-        nee_stats(stats, c, nullptr, zero, (uint64_t)n * (uint64_t)spp, 0, 0, 0, t_start);
-        return PT_OK;
-    }
-    // rays per launch
-    int64_t m_max = std::min<int64_t>(n, ((1ll << 31) - 1) / spp);
-    m_max = std::min<int64_t>(m_max, (int64_t)(batch_bytes_budget(c->device, false) / (3 * sizeof(float) * (size_t)spp)));
-    if (!is_device) m_max = std::min(m_max, kQueryHostChunk);
-    if (const char* tc = hook_env("PT_TRACE_CHUNK"))
-        if (*tc) m_max = std::min<int64_t>(m_max, strtoll(tc, nullptr, 10));
-    m_max = std::max<int64_t>(m_max, 1);
+    if (int rc = caller_rays_ready(who, c, !origins || !dirs || !rgb_out)) return rc;
     const QueryScene sc = query_scene(c);
     NeeLights lights;
-    WalkPlan plan;
-    PathsLaunch l;
-    int rc;
-    if ((rc = nee_lights(c, &lights))) return rc;
-    if ((rc = nee_plan(false, sc, c->lds_usable, c->num_cus, m_max * spp, plan))) return rc;
-    if ((rc = ensure(&c->d_tslab, &c->tslab_floats, 3 * (size_t)(m_max * spp)))) return rc;
-    if ((rc = nee_setup(c, plan, (int32_t)spp, prm->depth, prm->seed, l))) return rc;
-    // host pointers: staging [origins 3][dirs 3][rgb 3] x m_max, and the states
-    float *s_org = nullptr, *s_dir = nullptr, *s_out = nullptr;
-    if (!is_device) {
-        if ((rc = ensure(&c->d_tbuf, &c->tbuf_floats, 9 * (size_t)m_max))) return rc;
-        s_org = c->d_tbuf;
-        s_dir = s_org + 3 * m_max;
-        s_out = s_dir + 3 * m_max;
-        if (prm->states && (rc = ensure(&c->d_tstates, &c->tstates_words, (size_t)(m_max * spp)))) return rc;
-    }
-    EventPair ev, ev2;
-    HIP_TRY(hipEventCreate(&ev.a));
-    HIP_TRY(hipEventCreate(&ev.b));
-    HIP_TRY(hipEventCreate(&ev2.a));
-    double kernel_ms = 0, reduce_ms = 0;
-    int launches = 0;
-    for (int64_t i0 = 0; i0 < n; i0 += m_max) {
-        const int32_t m = (int32_t)std::min(m_max, n - i0);
-        l.m = m;
-        l.ray_base = (uint32_t)i0;
-        l.org = origins + 3 * i0;
-        l.dir = dirs + 3 * i0;
-        l.states = prm->states ? prm->states + i0 * spp : nullptr;
-        float* k_out = rgb_out + 3 * i0;
-        if (!is_device) {
-            HIP_TRY(hipMemcpyAsync(s_org, l.org, 3 * sizeof(float) * (size_t)m, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(s_dir, l.dir, 3 * sizeof(float) * (size_t)m, hipMemcpyHostToDevice, c->stream));
-            if (prm->states) {
-                HIP_TRY(hipMemcpyAsync(c->d_tstates, l.states, sizeof(uint32_t) * (size_t)(m * spp), hipMemcpyHostToDevice,
-                                       c->stream));
-                l.states = reinterpret_cast<const uint32_t*>(c->d_tstates);
-            }
-            l.org = s_org;
-            l.dir = s_dir;
-            k_out = s_out;
-        }
-        HIP_TRY(hipMemsetAsync(c->d_nctr, 0, sizeof(unsigned long long), c->stream));  // work head only
-        HIP_TRY(hipEventRecord(ev.a, c->stream));
-        if ((rc = nee_launch(c->stream, sc, plan, l, lights, 0, nullptr, nullptr, nullptr))) return rc;
-        HIP_TRY(hipEventRecord(ev.b, c->stream));
-        // the ray's samples in order from +0, then / spp (image.h:27-31, 37-40)
-        hipLaunchKernelGGL(pt_accumulate_kernel, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->d_tslab,
-                           (float*)nullptr, k_out, (int)m, (int)spp, 1, 1, 0, (float)spp, (const uint32_t*)nullptr, 0);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(ev2.a, c->stream));
-        launches++;
-        if (!is_device)
-            HIP_TRY(hipMemcpyAsync(rgb_out + 3 * i0, s_out, 3 * sizeof(float) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
-        kernel_ms += ms;
-        HIP_TRY(hipEventElapsedTime(&ms, ev.b, ev2.a));
-        reduce_ms += ms;
-    }
-    unsigned long long h_ctr[6] = {0, 0, 0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h_ctr, c->d_nctr, sizeof(h_ctr), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    nee_stats(stats, c, &plan, h_ctr, (uint64_t)n * (uint64_t)spp, kernel_ms, reduce_ms, launches, t_start);
-    if (h_ctr[3] != 0)
-        return set_error(PT_E_RUNAWAY, "%llu specular rejection loops hit the %d-iteration bound", h_ctr[3],
-                         kMaxSpecularIters);
-    return PT_OK;
+    CallerRays R{who, origins, dirs, n, prm, rgb_out, is_device, 0, false, t_start};
+    const int rc = caller_rays(
+        c, R, stats ? &stats->trace : nullptr,
+        [&](int64_t items, WalkPlan& plan) {
+            if (int lrc = nee_lights(c, &lights)) return lrc;
+            return nee_plan(false, sc, c->lds_usable, c->num_cus, items, plan);
+        },
+        [&](const PathsLaunch& l) { return nee_launch(c->stream, sc, R.plan, l, lights, 0, nullptr, nullptr, nullptr); });
+    if (stats && (rc == PT_OK || rc == PT_E_RUNAWAY)) nee_light_stats(stats, c, R.ctr);
+    return rc;
 }
 
 // The estimator along the part's own camera rays: pt_nee_cam_kernel fills a dense slab
@@ -2171,13 +2182,11 @@ int pt_ctx_render_nee(pt_ctx* c, const pt_camera* cam, const pt_params* prm, flo
     NeeLights lights;
     WalkPlan plan;
     PathsLaunch l;
-    unsigned long long h_ctr[6] = {0, 0, 0, 0, 0, 0};
+    unsigned long long h_ctr[kTraceCounters] = {};
     double kernel_ms = 0, reduce_ms = 0;
     int launches = 0;
-    EventPair ev, ev2;
-    HIP_TRY(hipEventCreate(&ev.a));
-    HIP_TRY(hipEventCreate(&ev.b));
-    HIP_TRY(hipEventCreate(&ev2.a));
+    LaunchTimer timer;
+    if ((rc = timer.create())) return rc;
     const auto accumulate = [&](int count, int first, int last) {
         if (moments)
             hipLaunchKernelGGL(pt_accumulate_moments_kernel, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream,
@@ -2196,147 +2205,79 @@ int pt_ctx_render_nee(pt_ctx* c, const pt_camera* cam, const pt_params* prm, flo
         if ((rc = nee_lights(c, &lights))) return rc;
         if ((rc = nee_plan(true, sc, c->lds_usable, c->num_cus, (int64_t)npix * c_max, plan))) return rc;
         if ((rc = ensure(&c->d_tslab, &c->tslab_floats, nval * (size_t)c_max))) return rc;
-        if ((rc = nee_setup(c, plan, 0, prm->depth, prm->seed, l))) return rc;
+        if (plan.stack_ints > 0 && (rc = ensure(&c->d_qstack, &c->qstack_ints, plan.stack_ints))) return rc;
+        if ((rc = trace_counters(c))) return rc;
+        if ((rc = paths_launch_base(c, 0, prm->depth, prm->seed, c->d_tslab, c->d_tctr, nullptr, 0, l))) return rc;
         l.m = npix;
         for (int s0 = 0; s0 < spp; s0 += (int)c_max) {
             const int sc_n = (int)std::min<int64_t>(c_max, spp - s0);
             l.spp = sc_n;
-            HIP_TRY(hipMemsetAsync(c->d_nctr, 0, sizeof(unsigned long long), c->stream));  // work head only
-            HIP_TRY(hipEventRecord(ev.a, c->stream));
+            HIP_TRY(hipMemsetAsync(c->d_tctr, 0, sizeof(unsigned long long), c->stream));  // work head only
+            if ((rc = timer.mark(0, c->stream))) return rc;
             if ((rc = nee_launch(c->stream, sc, plan, l, lights, s0, cam, prm, &shape))) return rc;
-            HIP_TRY(hipEventRecord(ev.b, c->stream));
+            if ((rc = timer.mark(1, c->stream))) return rc;
             accumulate(sc_n, s0 == 0 ? 1 : 0, s0 + sc_n == spp ? 1 : 0);
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(ev2.a, c->stream));
+            if ((rc = timer.mark(2, c->stream))) return rc;
             launches++;
             HIP_TRY(hipStreamSynchronize(c->stream));
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
-            kernel_ms += ms;
-            HIP_TRY(hipEventElapsedTime(&ms, ev.b, ev2.a));
-            reduce_ms += ms;
+            if ((rc = timer.add(&kernel_ms, &reduce_ms))) return rc;
         }
-        HIP_TRY(hipMemcpyAsync(h_ctr, c->d_nctr, sizeof(h_ctr), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(h_ctr, c->d_tctr, sizeof(h_ctr), hipMemcpyDeviceToHost, c->stream));
     }
-    // the image and the moments to the caller (moments_export's copies, with n = spp)
-    const hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    // the image and the moments (n = spp) to the caller
     if (!is_device) HIP_TRY(hipMemcpyAsync(img_out, dst, sizeof(float) * nval, hipMemcpyDeviceToHost, c->stream));
-    if (moments) {
-        if (mom->sum) HIP_TRY(hipMemcpyAsync(mom->sum, c->d_mom, nval * sizeof(double), kind, c->stream));
-        if (mom->sumsq) HIP_TRY(hipMemcpyAsync(mom->sumsq, c->d_mom + nval, nval * sizeof(double), kind, c->stream));
-        if (mom->sem) {
-            if (!is_device && (rc = ensure(&c->d_sem, &c->sem_floats, nval))) return rc;
-            float* sem = is_device ? mom->sem : c->d_sem;
-            hipLaunchKernelGGL(pt_moments_sem_kernel, dim3((unsigned)((nval + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
-                               c->d_mom, nval, spp, sem);
-            HIP_TRY(hipGetLastError());
-            if (!is_device) HIP_TRY(hipMemcpyAsync(mom->sem, sem, nval * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        }
-    }
+    if ((rc = moments_export(c, moments ? mom : nullptr, is_device, npix, spp))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    nee_stats(stats, c, prm->depth > 0 ? &plan : nullptr, h_ctr, (uint64_t)npix * (uint64_t)spp, kernel_ms, reduce_ms, launches,
-              t_start);
-    if (h_ctr[3] != 0)
-        return set_error(PT_E_RUNAWAY, "%llu specular rejection loops hit the %d-iteration bound", h_ctr[3],
-                         kMaxSpecularIters);
-    return PT_OK;
+    if (stats) {
+        fill_trace_stats(&stats->trace, prm->depth > 0 ? &plan : nullptr, false, h_ctr, (uint64_t)npix * (uint64_t)spp, kernel_ms,
+                         reduce_ms, launches, t_start);
+        nee_light_stats(stats, c, h_ctr);
+    }
+    return runaway_result(h_ctr[3]);
 }
 
 // Material gradients of trace() along the caller's rays (pt_grad.hip):
-// pt_ctx_trace's launches with pt_grad_kernel in place of pt_paths_kernel. Before them the
-// gradient table is zeroed and, with an override, the per-call materials are gathered; after
+// pt_grad_kernel under the shared loop, with grad_rgb staged beside the rays. Before the launches
+// the gradient table is zeroed and, with an override, the per-call materials are gathered; after
 // them the table is split into the caller's two arrays.
 int pt_ctx_trace_grad(pt_ctx* c, const float* origins, const float* dirs, int64_t n, const pt_trace_params* prm,
                       const pt_trace_grad_io* io, int is_device, pt_grad_stats* stats) {
     const auto t_start = std::chrono::steady_clock::now();
     if (stats) memset(stats, 0, sizeof(*stats));
-    if (!c) return set_error(PT_E_ARG, "pt_ctx_trace_grad: context is NULL");
-    if (!prm) return set_error(PT_E_ARG, "pt_ctx_trace_grad: params is NULL");
-    if (!io) return set_error(PT_E_ARG, "pt_ctx_trace_grad: io is NULL");
-    if (n < 0) return set_error(PT_E_ARG, "pt_ctx_trace_grad: n = %lld is negative", (long long)n);
-    if (prm->depth < 0 || prm->depth > PT_MAX_DEPTH)
-        return set_error(PT_E_ARG, "pt_ctx_trace_grad: depth %d outside 0..%d", prm->depth, PT_MAX_DEPTH);
-    if (prm->spp < 1 || prm->spp > kTraceMaxSpp)
-        return set_error(PT_E_ARG, "pt_ctx_trace_grad: spp %d outside 1..%d", prm->spp, kTraceMaxSpp);
-    if (!c->have_scene) return set_error(PT_E_ARG, "pt_ctx_trace_grad: no scene set");
+    static const char who[] = "pt_ctx_trace_grad";
+    if (int rc = caller_rays_check(who, c, prm, io ? nullptr : "io", n)) return rc;
     const bool want_grad = io->grad_color || io->grad_emit;
     if (want_grad && !io->grad_rgb && n > 0)
         return set_error(PT_E_ARG, "pt_ctx_trace_grad: grad_rgb is NULL but a gradient is asked for");
-    if (n > 0 && (!origins || !dirs)) return set_error(PT_E_ARG, "pt_ctx_trace_grad: NULL argument");
-    if (int rc0 = ctx_ready(c)) return rc0;
-    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = caller_rays_ready(who, c, n > 0 && (!origins || !dirs))) return rc;
     const int32_t T = c->meta.num_tris;  // the caller's triangles (one tri_idx position each)
     const size_t g_bytes = 3 * sizeof(double) * (size_t)T;
-    const int64_t spp = prm->spp;
-    auto zero_out = [&](void* p, size_t bytes) -> int {
-        if (!p) return PT_OK;
-        if (is_device) HIP_TRY(hipMemsetAsync(p, 0, bytes, c->stream));
-        else memset(p, 0, bytes);
-        return PT_OK;
-    };
-    auto finish = [&](const GradPlan* plan, const unsigned long long* ctr, double kms, double rms, double gms, int launches) {
-        if (!stats) return;
-        stats->trace.rays = ctr[1];
-        stats->trace.paths = (uint64_t)n * (uint64_t)spp;
-        stats->trace.runaway = ctr[3];
-        stats->trace.kernel_ms = kms;
-        stats->trace.reduce_ms = rms;
-        stats->trace.launches = launches;
-        stats->terms = ctr[2];
-        stats->grad_ms = gms;
-        if (plan) {
-            stats->trace.lds_scene = plan->walk.lds_scene;
-            stats->trace.lds_stack = plan->walk.lds_stack;
-            stats->trace.lds_records = plan->walk.lds_rec;
-            stats->lds_table = plan->lds_tab;
-        }
-        stats->trace.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-    };
-    int rc;
-    if (n == 0 || prm->depth == 0) {  // no ray is traced: every output +0 (render.h:37)
-        if ((rc = zero_out(io->grad_color, g_bytes)) || (rc = zero_out(io->grad_emit, g_bytes))) return rc;
-        if (n > 0 && (rc = zero_out(io->rgb_out, 3 * sizeof(float) * (size_t)n))) return rc;
-        if (is_device) HIP_TRY(hipStreamSynchronize(c->stream));
-        const unsigned long long zero[4] = {0, 0, 0, 0};
-        finish(nullptr, zero, 0, 0, 0, 0);
-        return PT_OK;
-    }
-    // rays per launch, as pt_ctx_trace cuts them
-    int64_t m_max = std::min<int64_t>(n, ((1ll << 31) - 1) / spp);
-    m_max = std::min<int64_t>(m_max, (int64_t)(batch_bytes_budget(c->device, false) / (3 * sizeof(float) * (size_t)spp)));
-    if (!is_device) m_max = std::min(m_max, kQueryHostChunk);
-    if (const char* tc = hook_env("PT_TRACE_CHUNK"))
-        if (*tc) m_max = std::min<int64_t>(m_max, strtoll(tc, nullptr, 10));
-    m_max = std::max<int64_t>(m_max, 1);
     const QueryScene sc = query_scene(c);
+    pt_trace_stats* ts = stats ? &stats->trace : nullptr;
     GradPlan plan;
-    if ((rc = grad_plan(sc, T, c->lds_usable, c->num_cus, prm->depth, m_max * spp, plan))) return rc;
-    if (plan.walk.stack_ints > 0 && (rc = ensure(&c->d_qstack, &c->qstack_ints, plan.walk.stack_ints))) return rc;
-    if (plan.walk.rec_words > 0 && (rc = ensure(&c->d_trec, &c->trec_words, 2 * plan.walk.rec_words))) return rc;
-    if ((rc = ensure(&c->d_tslab, &c->tslab_floats, 3 * (size_t)(m_max * spp)))) return rc;
+    CallerRays R{who, origins, dirs, n, prm, io->rgb_out, is_device, 0, true, t_start};
+    int rc;
+    if (n == 0 || prm->depth == 0)  // no ray is traced: the gradients are +0 as well (caller_rays_begin waits for them)
+        if ((rc = zero_output(c, io->grad_color, g_bytes, is_device)) || (rc = zero_output(c, io->grad_emit, g_bytes, is_device)))
+            return rc;
+    if ((rc = caller_rays_begin(c, R, [&](int64_t items, WalkPlan& walk) {
+            const int prc = grad_plan(sc, T, c->lds_usable, c->num_cus, prm->depth, items, plan);
+            walk = plan.walk;
+            return prc;
+        })))
+        return rc;
+    if (R.m_max == 0) return caller_rays_stats(R, ts);
     if ((rc = ensure(&c->d_gtab, &c->gtab_doubles, 12 * (size_t)T))) return rc;  // table, then the split outputs
-    if (!c->d_tctr) HIP_TRY(hipMalloc((void**)&c->d_tctr, 4 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemsetAsync(c->d_tctr, 0, 4 * sizeof(unsigned long long), c->stream));
-    // host pointers: pt_ctx_trace's staging of the rays and results, and [color 3T][emit 3T][grad_rgb 3 m_max]
-    float *s_org = nullptr, *s_dir = nullptr, *s_out = nullptr, *s_grgb = nullptr;
+    // host pointers: [color 3T][emit 3T][grad_rgb 3 m_max] beside the loop's staging
+    float* s_grgb = nullptr;
     const float *d_color = io->color, *d_emit = io->emit;
     if (!is_device) {
-        if ((rc = ensure(&c->d_tbuf, &c->tbuf_floats, 9 * (size_t)m_max))) return rc;
-        s_org = c->d_tbuf;
-        s_dir = s_org + 3 * m_max;
-        s_out = s_dir + 3 * m_max;
-        if (prm->states && (rc = ensure(&c->d_tstates, &c->tstates_words, (size_t)(m_max * spp)))) return rc;
-        if ((rc = ensure(&c->d_gbuf, &c->gbuf_floats, 6 * (size_t)T + 3 * (size_t)m_max))) return rc;
+        if ((rc = ensure(&c->d_gbuf, &c->gbuf_floats, 6 * (size_t)T + 3 * (size_t)R.m_max))) return rc;
         s_grgb = c->d_gbuf + 6 * (size_t)T;
     }
-    EventPair evg, evs, ev, ev2;
-    HIP_TRY(hipEventCreate(&evg.a));
-    HIP_TRY(hipEventCreate(&evg.b));
-    HIP_TRY(hipEventCreate(&evs.a));
-    HIP_TRY(hipEventCreate(&evs.b));
-    HIP_TRY(hipEventCreate(&ev.a));
-    HIP_TRY(hipEventCreate(&ev.b));
-    HIP_TRY(hipEventCreate(&ev2.a));
+    EventPair evg, evs;
+    if ((rc = evg.create()) || (rc = evs.create())) return rc;
     HIP_TRY(hipEventRecord(evg.a, c->stream));
     HIP_TRY(hipMemsetAsync(c->d_gtab, 0, 6 * sizeof(double) * (size_t)T, c->stream));
     const f4* mats = sc.mats;
@@ -2358,74 +2299,27 @@ int pt_ctx_trace_grad(pt_ctx* c, const float* origins, const float* dirs, int64_
     }
     HIP_TRY(hipEventRecord(evg.b, c->stream));
     GradLaunch gl{};
-    PathsLaunch& l = gl.p;
-    l.spp = (int32_t)spp;
-    l.depth = prm->depth;
-    l.seed = prm->seed;
-    l.slab = c->d_tslab;
-    l.ctr = c->d_tctr;
-    l.gstack = c->d_qstack;
-    l.grec = plan.walk.rec_words > 0 ? c->d_trec : nullptr;
-    l.dark = 0;
-    l.force_exact = query_force_exact();
-    {
-        const float2* tab = nullptr;
-        if ((rc = theta_choice(c, &l.theta_lanes, &tab))) return rc;
-        l.theta_tab = tab;
-    }
     gl.mats = mats;
     gl.table = c->d_gtab;
     gl.table_rows = T;
     gl.want_rgb = io->rgb_out ? 1 : 0;
     gl.want_color = io->grad_color ? 1 : 0;
     gl.want_emit = io->grad_emit ? 1 : 0;
-    double kernel_ms = 0, reduce_ms = 0, grad_ms = 0;
-    int launches = 0;
-    for (int64_t i0 = 0; i0 < n; i0 += m_max) {
-        const int32_t m = (int32_t)std::min(m_max, n - i0);
-        l.m = m;
-        l.ray_base = (uint32_t)i0;
-        l.org = origins + 3 * i0;
-        l.dir = dirs + 3 * i0;
-        l.states = prm->states ? prm->states + i0 * spp : nullptr;
-        gl.grad_rgb = want_grad ? io->grad_rgb + 3 * i0 : nullptr;
-        float* k_out = io->rgb_out ? io->rgb_out + 3 * i0 : nullptr;
-        if (!is_device) {
-            HIP_TRY(hipMemcpyAsync(s_org, l.org, 3 * sizeof(float) * (size_t)m, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(s_dir, l.dir, 3 * sizeof(float) * (size_t)m, hipMemcpyHostToDevice, c->stream));
-            if (prm->states) {
-                HIP_TRY(hipMemcpyAsync(c->d_tstates, l.states, sizeof(uint32_t) * (size_t)(m * spp), hipMemcpyHostToDevice,
-                                       c->stream));
-                l.states = reinterpret_cast<const uint32_t*>(c->d_tstates);
-            }
-            if (want_grad) {
+    rc = caller_rays_loop(
+        c, R,
+        [&](const PathsLaunch& l) {
+            gl.p = l;
+            return grad_launch(c->stream, sc, plan, gl);
+        },
+        [&](int64_t i0, int32_t m) -> int {
+            gl.grad_rgb = want_grad ? io->grad_rgb + 3 * i0 : nullptr;
+            if (want_grad && !is_device) {
                 HIP_TRY(hipMemcpyAsync(s_grgb, gl.grad_rgb, 3 * sizeof(float) * (size_t)m, hipMemcpyHostToDevice, c->stream));
                 gl.grad_rgb = s_grgb;
             }
-            l.org = s_org;
-            l.dir = s_dir;
-            k_out = io->rgb_out ? s_out : nullptr;
-        }
-        HIP_TRY(hipMemsetAsync(c->d_tctr, 0, sizeof(unsigned long long), c->stream));  // work head only
-        HIP_TRY(hipEventRecord(ev.a, c->stream));
-        if ((rc = grad_launch(c->stream, sc, plan, gl))) return rc;
-        HIP_TRY(hipEventRecord(ev.b, c->stream));
-        if (k_out) {  // the ray's samples in order from +0, then / spp (image.h:27-31, 37-40)
-            hipLaunchKernelGGL(pt_accumulate_kernel, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->d_tslab,
-                               (float*)nullptr, k_out, (int)m, (int)spp, 1, 1, 0, (float)spp, (const uint32_t*)nullptr, 0);
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipEventRecord(ev2.a, c->stream));
-        launches++;
-        if (!is_device && io->rgb_out)
-            HIP_TRY(hipMemcpyAsync(io->rgb_out + 3 * i0, s_out, 3 * sizeof(float) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
-        kernel_ms += ms;
-        HIP_TRY(hipEventElapsedTime(&ms, ev.b, ev2.a));
-        reduce_ms += ms;
-    }
+            return PT_OK;
+        });
+    if (rc) return rc;
     // the table's rows into the caller's two arrays
     HIP_TRY(hipEventRecord(evs.a, c->stream));
     if (want_grad) {
@@ -2438,23 +2332,17 @@ int pt_ctx_trace_grad(pt_ctx* c, const float* origins, const float* dirs, int64_
         }
     }
     HIP_TRY(hipEventRecord(evs.b, c->stream));
-    unsigned long long h_ctr[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h_ctr, c->d_tctr, sizeof(h_ctr), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, evg.a, evg.b));
-        grad_ms += ms;
-        HIP_TRY(hipEventElapsedTime(&ms, evs.a, evs.b));
-        grad_ms += ms;
+    if ((rc = caller_rays_end(c, R))) return rc;
+    if (stats) {
+        float gather_ms = 0, split_ms = 0;
+        HIP_TRY(hipEventElapsedTime(&gather_ms, evg.a, evg.b));
+        HIP_TRY(hipEventElapsedTime(&split_ms, evs.a, evs.b));
+        stats->terms = R.ctr[2];
+        stats->grad_ms = (double)gather_ms + (double)split_ms;
+        stats->lds_table = plan.lds_tab;
     }
-    finish(&plan, h_ctr, kernel_ms, reduce_ms, grad_ms, launches);
-    if (h_ctr[3] != 0)
-        return set_error(PT_E_RUNAWAY, "%llu specular rejection loops hit the %d-iteration bound", h_ctr[3],
-                         kMaxSpecularIters);
-    return PT_OK;
+    return caller_rays_stats(R, ts);
 }
-
 }  // extern "C"
 
 // ---------------------------------------------------------------- adaptive sampling
@@ -2496,22 +2384,20 @@ int adaptive_rounds(pt_ctx* c, const pt_camera* cam, const pt_params* prm, const
     if (!c->d_actr) HIP_TRY(hipMalloc((void**)&c->d_actr, 5 * sizeof(unsigned long long)));
     HIP_TRY(hipMemsetAsync(c->d_actr, 0, 5 * sizeof(unsigned long long), c->stream));
     unsigned long long* d_count = c->d_actr + 4;
-    EventPair ev, ev2;
-    HIP_TRY(hipEventCreate(&ev.a));
-    HIP_TRY(hipEventCreate(&ev.b));
-    HIP_TRY(hipEventCreate(&ev2.a));
+    LaunchTimer timer;
+    if ((rc = timer.create())) return rc;
     // the unconverged pixels of `prev` (m of them; nullptr: the part) after n samples -> d_alist[to]; 8 bytes read back
     auto compact = [&](const int32_t* prev, int32_t m, int32_t n_at, int to, int64_t* left) -> int {
         unsigned long long h = 0;
-        HIP_TRY(hipEventRecord(ev.a, c->stream));
+        if (int trc = timer.mark(0, c->stream)) return trc;
         if (int crc = adaptive_compact(c->stream, prev, m, c->d_mom, npix, n_at, cv->rel, cv->abs, c->d_alist[to], d_count,
                                        c->d_aspp))
             return crc;
-        HIP_TRY(hipEventRecord(ev.b, c->stream));
+        if (int trc = timer.mark(1, c->stream)) return trc;
         HIP_TRY(hipMemcpyAsync(&h, d_count, sizeof(h), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
+        HIP_TRY(hipEventElapsedTime(&ms, timer.e[0], timer.e[1]));
         S.reduce_ms += ms;
         *left = (int64_t)h;
         return PT_OK;
@@ -2522,17 +2408,8 @@ int adaptive_rounds(pt_ctx* c, const pt_camera* cam, const pt_params* prm, const
     S.samples = (int64_t)(npix - m) * n;
 
     const QueryScene sc = query_scene(c);
-    PathsLaunch l{};
-    l.depth = prm->depth;
-    l.seed = prm->seed;
-    l.ctr = c->d_actr;
-    l.dark = c->dark ? 1 : 0;
-    l.force_exact = query_force_exact();
-    {
-        const float2* tab = nullptr;
-        if ((rc = theta_choice(c, &l.theta_lanes, &tab))) return rc;
-        l.theta_tab = tab;
-    }
+    PathsLaunch l;  // slab, stack and records: each round's own, below
+    if ((rc = paths_launch_base(c, 0, prm->depth, prm->seed, nullptr, c->d_actr, nullptr, c->dark ? 1 : 0, l))) return rc;
     // items (listed pixels x samples) per launch: the slab budget and the 2^31-item bound;
     // PT_ADAPTIVE_CHUNK (test hook): the items themselves
     int64_t items_max = std::min<int64_t>((1ll << 31) - 1, (int64_t)(batch_bytes_budget(c->device, false) / (3 * sizeof(float))));
@@ -2559,20 +2436,18 @@ int adaptive_rounds(pt_ctx* c, const pt_camera* cam, const pt_params* prm, const
             for (int64_t s0 = n; s0 < n_next; s0 += c_l) {
                 l.spp = (int32_t)std::min<int64_t>(c_l, n_next - s0);
                 HIP_TRY(hipMemsetAsync(c->d_actr, 0, sizeof(unsigned long long), c->stream));  // work head only
-                HIP_TRY(hipEventRecord(ev.a, c->stream));
+                if ((rc = timer.mark(0, c->stream))) return rc;
                 if ((rc = adaptive_launch(c->stream, sc, plan, l, list, (int32_t)s0, cam, prm, shape))) return rc;
-                HIP_TRY(hipEventRecord(ev.b, c->stream));
+                if ((rc = timer.mark(1, c->stream))) return rc;
                 if ((rc = adaptive_accumulate(c->stream, c->d_aslab, list, l.m, l.spp, c->d_accum, c->d_mom, dst, npix,
                                               s0 + l.spp == n_next ? n_next : 0)))
                     return rc;
-                HIP_TRY(hipEventRecord(ev2.a, c->stream));
+                if ((rc = timer.mark(2, c->stream))) return rc;
                 HIP_TRY(hipStreamSynchronize(c->stream));
-                float ms = 0;
-                HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
-                S.kernel_ms += ms;
-                S.sparse_kernel_ms += ms;
-                HIP_TRY(hipEventElapsedTime(&ms, ev.b, ev2.a));
-                S.reduce_ms += ms;
+                double kernel_ms = 0;
+                if ((rc = timer.add(&kernel_ms, &S.reduce_ms))) return rc;
+                S.kernel_ms += kernel_ms;
+                S.sparse_kernel_ms += kernel_ms;
                 S.sparse_launches++;
             }
         }
@@ -2655,7 +2530,7 @@ int pt_ctx_render_adaptive(pt_ctx* c, const pt_camera* cam, const pt_params* prm
                                out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (int xrc = moments_export(c, mom, out_is_device, sparse ? c->d_aspp : nullptr)) return xrc;
+    if (int xrc = moments_export(c, mom, out_is_device, npix, c->prog_spp, sparse ? c->d_aspp : nullptr)) return xrc;
     S.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     if (as) *as = S;
     if (runaway)

@@ -89,6 +89,16 @@ def _states(states, n: int, samples: int) -> Optional[np.ndarray]:
     return st
 
 
+def _host_rays(origins, directions, depth: int, samples: int, seed: int, states):
+    """The numpy arguments of a call along the caller's rays: (origins, directions, n, pt_trace_params,
+    the states array the params point into)."""
+    o, d = _rays(origins, directions)
+    n = o.shape[0]
+    st_arr = _states(states, n, samples)
+    prm = _lib.pt_trace_params(depth, samples, seed, st_arr.ctypes.data if st_arr is not None else None)
+    return o, d, n, prm, st_arr
+
+
 def _is_tensor(x) -> bool:
     return hasattr(x, "data_ptr")
 
@@ -300,31 +310,21 @@ class BVH:
         (rgb (n, 3) float32, stats). rgb[i] is the float32 sum of `samples` paths of ray i in
         order, divided by `samples`; sample s of ray i starts the LCG at states[i, s] (uint32,
         (n, samples)) or, with states None, at pt_sample_seed(i, s, seed)."""
-        ref = _SceneRef(self)
-        o, d = _rays(origins, directions)
-        n = o.shape[0]
-        st_arr = _states(states, n, samples)
-        prm = _lib.pt_trace_params(depth, samples, seed, st_arr.ctypes.data if st_arr is not None else None)
-        rgb = np.empty((n, 3), dtype=np.float32)
-        st = _lib.pt_trace_stats()
-        check(lib().pt_bvh_trace(C.byref(ref.s), o.ctypes.data, d.ctypes.data, n, C.byref(prm), rgb.ctypes.data,
-                                 C.byref(st)))
-        return rgb, st.as_dict()
+        return self._trace_host(lib().pt_bvh_trace, _lib.pt_trace_stats, origins, directions, depth, samples, seed, states)
 
     def trace_nee(self, origins, directions, depth: int, samples: int = 1, seed: int = PT_SEED, states=None):
         """The light-sampling estimator (include/pt_hip.h: next-event estimation, the same expected
         value as trace() at every depth) along a batch of rays on the host (pt_bvh_trace_nee; no
         device needed), bit-identical to Renderer.trace_nee. Arguments and result as trace(); the
         stats also count shadow_rays and light_draws (rays = path and shadow segments together)."""
+        return self._trace_host(lib().pt_bvh_trace_nee, _lib.pt_nee_stats, origins, directions, depth, samples, seed, states)
+
+    def _trace_host(self, fn, stats_type, origins, directions, depth, samples, seed, states):
         ref = _SceneRef(self)
-        o, d = _rays(origins, directions)
-        n = o.shape[0]
-        st_arr = _states(states, n, samples)
-        prm = _lib.pt_trace_params(depth, samples, seed, st_arr.ctypes.data if st_arr is not None else None)
+        o, d, n, prm, _keep = _host_rays(origins, directions, depth, samples, seed, states)
         rgb = np.empty((n, 3), dtype=np.float32)
-        st = _lib.pt_nee_stats()
-        check(lib().pt_bvh_trace_nee(C.byref(ref.s), o.ctypes.data, d.ctypes.data, n, C.byref(prm), rgb.ctypes.data,
-                                     C.byref(st)))
+        st = stats_type()
+        check(fn(C.byref(ref.s), o.ctypes.data, d.ctypes.data, n, C.byref(prm), rgb.ctypes.data, C.byref(st)))
         return rgb, st.as_dict()
 
     def trace_grad(self, origins, directions, grad_rgb, depth: int, samples: int = 1, seed: int = PT_SEED, states=None,
@@ -332,10 +332,7 @@ class BVH:
         """Renderer.trace_grad on the host (pt_bvh_trace_grad; no device needed): the same
         per-path terms, summed in double in (ray, sample, bounce) order."""
         ref = _SceneRef(self)
-        o, d = _rays(origins, directions)
-        n = o.shape[0]
-        st_arr = _states(states, n, samples)
-        prm = _lib.pt_trace_params(depth, samples, seed, st_arr.ctypes.data if st_arr is not None else None)
+        o, d, n, prm, _st = _host_rays(origins, directions, depth, samples, seed, states)
         io, res, _keep = _grad_io_host(len(self.triangles), n, grad_rgb, color, emit, want)
         st = _lib.pt_grad_stats()
         check(lib().pt_bvh_trace_grad(C.byref(ref.s), o.ctypes.data, d.ctypes.data, n, C.byref(prm), C.byref(io),
@@ -665,7 +662,9 @@ class Renderer:
         ((t, tri), stats), or (occluded, stats) with any_hit (int32 0 / 1: t < tmax, tmax (n,)
         or None = 1e30). Contiguous float32 torch tensors on this context's device go through
         the device-pointer path: `out` = (t, tri) tensors (float32, int32), or the int32
-        `occluded` tensor with any_hit, written in place and returned."""
+        `occluded` tensor with any_hit, written in place and returned. Tensors follow the rule of
+        the device-pointer paths: on the context's device, and torch's current stream is waited for
+        before they are read."""
         st = _lib.pt_query_stats()
         mode = _lib.PT_QUERY_ANY if any_hit else _lib.PT_QUERY_CLOSEST
         if _is_tensor(origins):
@@ -676,11 +675,9 @@ class Renderer:
                 tri = torch.empty(n, dtype=torch.int32, device=origins.device)
                 out = tri if any_hit else (torch.empty(n, dtype=torch.float32, device=origins.device), tri)
             outs = [out] if any_hit else list(out)
-            for x in tens + outs:
-                if not x.is_contiguous() or not x.is_cuda or x.element_size() != 4:
-                    raise ValueError("tensors must be contiguous 32-bit tensors on the context's device")
-            if directions.numel() != 3 * n or any(x.numel() != n for x in tens[2:] + outs):
-                raise ValueError("directions must hold n x 3 elements, tmax and the outputs n")
+            self._device_tensors([(origins, None), (directions, 3 * n)] + [(x, n) for x in tens[2:] + outs],
+                                 "tensors must be contiguous 32-bit tensors on the context's device",
+                                 "directions must hold n x 3 elements, tmax and the outputs n")
             ptrs = [C.c_void_p(x.data_ptr()) for x in tens + outs]
             check(lib().pt_ctx_intersect(self.h, ptrs[0], ptrs[1], n, mode, ptrs[2] if tmax is not None else None,
                                          None if any_hit else ptrs[-2], ptrs[-1], 1, C.byref(st)))
@@ -707,59 +704,49 @@ class Renderer:
         pt_sample_seed(i, s, seed). numpy arrays go through host pointers. Contiguous torch
         tensors on this context's device (float32 rays, `states` of a 32-bit integer type) go
         through the device-pointer path: `out`, a float32 tensor of n x 3 elements, is written
-        in place and returned, and the inputs are left untouched."""
-        st = _lib.pt_trace_stats()
-        if _is_tensor(origins):
-            n = origins.numel() // 3
-            if out is None:
-                import torch
-                out = torch.empty((n, 3), dtype=torch.float32, device=origins.device)
-            tens = [origins, directions, out] + ([states] if states is not None else [])
-            for x in tens:
-                if not x.is_contiguous() or not x.is_cuda or x.element_size() != 4:
-                    raise ValueError("tensors must be contiguous 32-bit tensors on the context's device")
-            if directions.numel() != 3 * n or out.numel() != 3 * n or (states is not None and states.numel() != n * samples):
-                raise ValueError("directions and out must hold n x 3 elements, states n x samples")
-            prm = _lib.pt_trace_params(depth, samples, seed, states.data_ptr() if states is not None else None)
-            check(lib().pt_ctx_trace(self.h, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()), n,
-                                     C.byref(prm), C.c_void_p(out.data_ptr()), 1, C.byref(st)))
-            return out, st.as_dict()
-        o, d = _rays(origins, directions)
-        n = o.shape[0]
-        st_arr = _states(states, n, samples)
-        prm = _lib.pt_trace_params(depth, samples, seed, st_arr.ctypes.data if st_arr is not None else None)
-        rgb = np.empty((n, 3), dtype=np.float32)
-        check(lib().pt_ctx_trace(self.h, o.ctypes.data, d.ctypes.data, n, C.byref(prm), rgb.ctypes.data, 0, C.byref(st)))
-        return rgb, st.as_dict()
+        in place and returned, and the inputs are left untouched. Tensors follow the rule of the
+        device-pointer paths: on the context's device, and torch's current stream is waited for
+        before they are read."""
+        return self._caller_rays(lib().pt_ctx_trace, _lib.pt_trace_stats, origins, directions, depth, samples, seed, states, out)
 
     def trace_nee(self, origins, directions, depth: int, samples: int = 1, seed: int = PT_SEED, states=None, out=None):
         """The light-sampling estimator (include/pt_hip.h) along a batch of the caller's rays on
         this context's scene (pt_ctx_trace_nee): arguments, numpy and tensor paths as trace(),
         bit-identical to BVH.trace_nee. Tensors follow the rule of the device-pointer paths: on
         the context's device, and torch's current stream is waited for before they are read."""
-        st = _lib.pt_nee_stats()
+        return self._caller_rays(lib().pt_ctx_trace_nee, _lib.pt_nee_stats, origins, directions, depth, samples, seed, states, out)
+
+    def _device_tensors(self, items, message: str, count_message: Optional[str] = None, dtype=None) -> None:
+        """The checks of a tensor path on (tensor, element count or None) pairs: each a contiguous
+        CUDA tensor of a 32-bit type (or of `dtype`), else ValueError(message); each of its count,
+        else ValueError(count_message or message); then the rule of `_own_device_tensors`."""
+        for x, _ in items:
+            if not _is_tensor(x) or not x.is_contiguous() or not x.is_cuda or \
+                    (x.element_size() != 4 if dtype is None else x.dtype != dtype):
+                raise ValueError(message)
+        if any(cnt is not None and x.numel() != cnt for x, cnt in items):
+            raise ValueError(count_message or message)
+        _own_device_tensors(self.device, *(x for x, _ in items))
+
+    def _caller_rays(self, fn, stats_type, origins, directions, depth, samples, seed, states, out):
+        """pt_ctx_trace or pt_ctx_trace_nee (`fn`) along the caller's rays: the tensor path and the numpy path."""
+        st = stats_type()
         if _is_tensor(origins):
             n = origins.numel() // 3
             if out is None:
                 import torch
                 out = torch.empty((n, 3), dtype=torch.float32, device=origins.device)
-            tens = [origins, directions, out] + ([states] if states is not None else [])
-            for x in tens:
-                if not _is_tensor(x) or not x.is_contiguous() or not x.is_cuda or x.element_size() != 4:
-                    raise ValueError("tensors must be contiguous 32-bit tensors on the context's device")
-            if directions.numel() != 3 * n or out.numel() != 3 * n or (states is not None and states.numel() != n * samples):
-                raise ValueError("directions and out must hold n x 3 elements, states n x samples")
-            _own_device_tensors(self.device, *tens)
+            self._device_tensors([(origins, None), (directions, 3 * n), (out, 3 * n)] +
+                                 ([(states, n * samples)] if states is not None else []),
+                                 "tensors must be contiguous 32-bit tensors on the context's device",
+                                 "directions and out must hold n x 3 elements, states n x samples")
             prm = _lib.pt_trace_params(depth, samples, seed, states.data_ptr() if states is not None else None)
-            check(lib().pt_ctx_trace_nee(self.h, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()), n,
-                                         C.byref(prm), C.c_void_p(out.data_ptr()), 1, C.byref(st)))
+            check(fn(self.h, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()), n, C.byref(prm),
+                     C.c_void_p(out.data_ptr()), 1, C.byref(st)))
             return out, st.as_dict()
-        o, d = _rays(origins, directions)
-        n = o.shape[0]
-        st_arr = _states(states, n, samples)
-        prm = _lib.pt_trace_params(depth, samples, seed, st_arr.ctypes.data if st_arr is not None else None)
+        o, d, n, prm, _keep = _host_rays(origins, directions, depth, samples, seed, states)
         rgb = np.empty((n, 3), dtype=np.float32)
-        check(lib().pt_ctx_trace_nee(self.h, o.ctypes.data, d.ctypes.data, n, C.byref(prm), rgb.ctypes.data, 0, C.byref(st)))
+        check(fn(self.h, o.ctypes.data, d.ctypes.data, n, C.byref(prm), rgb.ctypes.data, 0, C.byref(st)))
         return rgb, st.as_dict()
 
     def render_nee(self, camera: Camera, samples: int, depth: int, seed: int = PT_SEED, part_index: int = 0,
@@ -792,7 +779,9 @@ class Renderer:
         float64 = dLoss/d color, "emit": likewise} restricted to `want`, stats). Rays, samples,
         seed and states are trace()'s. numpy arrays go through host pointers; contiguous torch
         tensors on this context's device (every array argument then) through device pointers,
-        the results are tensors there, and the inputs are left untouched."""
+        the results are tensors there, and the inputs are left untouched. Tensors follow the rule
+        of the device-pointer paths: on the context's device, and torch's current stream is waited
+        for before they are read."""
         st = _lib.pt_grad_stats()
         if _is_tensor(origins):
             import torch
@@ -805,13 +794,11 @@ class Renderer:
                 if val is not None:
                     f32.append((val, cnt))
                     setattr(io, key, val.data_ptr())
-            for x, cnt in f32:
-                if not _is_tensor(x) or not x.is_contiguous() or not x.is_cuda or x.dtype != torch.float32 or x.numel() != cnt:
-                    raise ValueError("rays, color, emit and grad_rgb must be contiguous float32 tensors of n x 3 / "
-                                     "num_tris x 3 elements on the context's device")
-            if states is not None and (not states.is_contiguous() or not states.is_cuda or states.element_size() != 4
-                                       or states.numel() != n * samples):
-                raise ValueError("states must be a contiguous 32-bit tensor of n x samples elements on the context's device")
+            self._device_tensors(f32, "rays, color, emit and grad_rgb must be contiguous float32 tensors of n x 3 / "
+                                 "num_tris x 3 elements on the context's device", dtype=torch.float32)
+            if states is not None:
+                self._device_tensors([(states, n * samples)], "states must be a contiguous 32-bit tensor of n x samples "
+                                     "elements on the context's device")
             if ("color" in want or "emit" in want) and grad_rgb is None:
                 raise ValueError("grad_rgb is needed for the gradients")
             if "rgb" in want:
@@ -825,10 +812,7 @@ class Renderer:
             check(lib().pt_ctx_trace_grad(self.h, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()), n,
                                           C.byref(prm), C.byref(io), 1, C.byref(st)))
             return res, st.as_dict()
-        o, d = _rays(origins, directions)
-        n = o.shape[0]
-        st_arr = _states(states, n, samples)
-        prm = _lib.pt_trace_params(depth, samples, seed, st_arr.ctypes.data if st_arr is not None else None)
+        o, d, n, prm, _st = _host_rays(origins, directions, depth, samples, seed, states)
         io, res, _keep = _grad_io_host(self.num_tris, n, grad_rgb, color, emit, want)
         check(lib().pt_ctx_trace_grad(self.h, o.ctypes.data, d.ctypes.data, n, C.byref(prm), C.byref(io), 0, C.byref(st)))
         return res, st.as_dict()
