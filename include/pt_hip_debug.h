@@ -23,7 +23,16 @@ int pt_debug_math(int device, int which, const float* in, int n, float* out);
  * every float bit pattern in [lo_bits, hi_bits] (NaN inputs skipped), on `device`:
  * which = 0: rcp_exact(x) vs 1.0f / x;  1: sqrt_exact(x) vs sqrtf(x);
  *         2: acosf fast vs restatement;  3: sincosf fast vs restatement (pt_math.h);
- *         4: div_by_rcp(x, b, RN(1/b)) vs x / b for a hashed divisor b per input x.
+ *         4: div_by_rcp(x, b, RN(1/b)) vs x / b for a hashed divisor b per input x;
+ *         5: rcp3_exact on {x, x, x} vs 1.0f / x, the unit-vector form for |x| <= 2, the two-sided
+ *            form elsewhere;
+ *         6: rcp3_exact on {x, b, c} vs the three IEEE reciprocals, b and c hashed per input and, for
+ *            one input in 16, forced out of range (+-0, subnormal, 2^127, +-inf, (2^126, 2^128)), so
+ *            that every wave holds lanes on both sides of the wave-uniform fallback;
+ *         7: normalize_fast on {x, b, c} vs the IEEE square root and divisions, b and c in
+ *            [2^-40, 2^40] and forced as in 6;  8: the same without the forced inputs;
+ *         9: 6 without the forced inputs (waves keep the fast results), and with a NaN as b for one
+ *            input in 16: that component must come out NaN (any payload), the other two exact.
  * *mismatches = number of differing results, *first_bad = lowest differing input bits
  * (0xffffffff if none). */
 int pt_debug_sweep(int device, int which, uint32_t lo_bits, uint32_t hi_bits, uint64_t* mismatches,

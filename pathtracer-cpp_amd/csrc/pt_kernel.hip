@@ -294,6 +294,54 @@ __global__ void pt_sweep_kernel(int which, uint32_t lo, unsigned long long n, un
             same = __float_as_uint(div_by_rcp(x, b, rcp_exact(b))) == __float_as_uint(x / b);
         } else if (which == 2) {
             same = __float_as_uint(acosf_fast(x)) == __float_as_uint(acosf_ref(x));
+        } else if (which == 5) {
+            // rcp3_exact's two predicates on three equal components: the unit form (lower bound only)
+            // wherever a unit vector's component can lie, |x| <= 2, the two-sided form elsewhere
+            const v3 r = __builtin_fabsf(x) <= 2.0f ? rcp3_exact<true>(v3{x, x, x}) : rcp3_exact<false>(v3{x, x, x});
+            const uint32_t q = __float_as_uint(1.0f / x);
+            same = __float_as_uint(r.x) == q && __float_as_uint(r.y) == q && __float_as_uint(r.z) == q;
+        } else if (which >= 6 && which <= 9) {
+            // The wave-uniform fallback with a wave's lanes on both sides of the range: component 0 is
+            // x, components 1 and 2 are hashed normal floats (6, 9: of rcp_exact's whole range; 7, 8: of
+            // [2^-40, 2^40], where normalize_fast's fast path holds), and in 6 and 7 one input in 16
+            // (four lanes of every wave) has them forced to +-0, a subnormal, 2^127, +-inf or a value in
+            // (2^126, 2^128). 6: rcp3_exact, 7 and 8: normalize_fast, against the IEEE operations.
+            // 8 and 9 are 7 and 6 without the forced lanes, so that the waves of in-range x keep the
+            // fast results of three different components; in 9 one input in 16 has a NaN as component
+            // 1, which passes rcp3_exact's predicate beside two components in range: the result must
+            // be a NaN there (any payload) and the other two components exact.
+            const uint32_t h1 = pt_mix32(bits * 0x9e3779b9u + 0x7f4a7c15u), h2 = pt_mix32(h1 ^ 0x85ebca6bu);
+            auto pick = [&](uint32_t h, uint32_t k) {
+                const uint32_t sign = h & 0x80000000u, mant = h & 0x7fffffu;
+                if (which <= 7 && (bits & 15u) == 11u) {
+                    switch (k & 7u) {
+                        case 0: return __uint_as_float(sign);                              // +-0
+                        case 1: return __uint_as_float(sign | mant | 1u);                  // subnormal
+                        case 2: return 0x1p127f;
+                        case 3: return __uint_as_float(sign | 0x7f800000u);                // +-inf
+                        case 4: return __uint_as_float(sign | 0x7e800000u | mant | 1u);    // (2^126, 2^127)
+                        case 5: return __uint_as_float(sign | 0x7f000000u | mant);         // [2^127, 2^128)
+                        case 6: return __uint_as_float(sign | 1u);                         // smallest subnormal
+                        default: return __uint_as_float(0x80000000u);                      // -0
+                    }
+                }
+                const uint32_t e = (which == 6 || which == 9) ? 1u + (h >> 23) % 252u : 87u + (h >> 23) % 81u;
+                return __uint_as_float(sign | (e << 23) | mant);
+            };
+            v3 a{x, pick(h1, h1 >> 8), pick(h2, (h1 >> 8) + 3u)};
+            if (which == 9 && (bits & 15u) == 11u) a.y = __uint_as_float((h1 & 0x80000000u) | 0x7fc00000u | (h1 & 0x3fffffu));
+            v3 r, q;
+            if (which == 6 || which == 9) {
+                r = rcp3_exact<false>(a);
+                q = v3{1.0f / a.x, 1.0f / a.y, 1.0f / a.z};
+            } else {
+                r = normalize_fast(a);
+                const float len = __builtin_sqrtf(dot(a, a));
+                q = v3{a.x / len, a.y / len, a.z / len};
+            }
+            same = __float_as_uint(r.x) == __float_as_uint(q.x) &&
+                   (__float_as_uint(r.y) == __float_as_uint(q.y) || (which == 9 && r.y != r.y && q.y != q.y)) &&
+                   __float_as_uint(r.z) == __float_as_uint(q.z);
         } else {
             float s1, c1, s0, c0;
             sincosf_fast(x, s1, c1);
@@ -2742,7 +2790,7 @@ int pt_debug_math(int device, int which, const float* in, int n, float* out) {
 
 int pt_debug_sweep(int device, int which, uint32_t lo_bits, uint32_t hi_bits, uint64_t* mismatches,
                    uint32_t* first_bad) {
-    if (!mismatches || !first_bad || which < 0 || which > 4 || hi_bits < lo_bits)
+    if (!mismatches || !first_bad || which < 0 || which > 9 || hi_bits < lo_bits)
         return set_error(PT_E_ARG, "pt_debug_sweep: bad argument");
     HIP_TRY(hipSetDevice(device));
     unsigned long long* d_bad = nullptr;

@@ -58,21 +58,40 @@ PT_HD v3 cross(v3 a, v3 b) {
 //   rcp:  v_rcp_f32, then one Newton step with FMA; exact for |a| in [2^-126, 2^126]
 //   sqrt: v_sqrt_f32, then the +-1 ulp residual fix-up; exact for x in [2^-100, 2^100]
 // On the host (oracle, CPU builds) they are the IEEE operations themselves.
-PT_HD float rcp_exact(float a) {
+//
+// The fallback is chosen once per wave, not per lane (PT_WAVE_GUARD): every lane runs the
+// fast sequence, and when ANY active lane's input is out of range the whole wave runs the
+// IEEE operation too and keeps that. The two agree on every lane in range, so each lane
+// gets the bits the per-lane guard gave it, and the common case is straight-line code: one
+// or two compares and a scalar branch instead of a divergent if/else per call, and the
+// sequences of neighbouring calls share a basic block, where their v_rcp latencies overlap.
+#ifndef PT_WAVE_GUARD
+#define PT_WAVE_GUARD 1  // 0: a per-lane branch around every fast sequence (A/B hook)
+#endif
+#ifndef PT_ACOS_WAVE
+#define PT_ACOS_WAVE 1  // 0: acosf_fast with guarded inner operations and a per-lane early-out (A/B hook)
+#endif
+#ifndef PT_SINCOS_BITS
+#define PT_SINCOS_BITS 1  // 0: sincosf_fast with the |y| < 2^-12 selects and compared signs (A/B hook)
+#endif
+
+// Whether `p` holds in some active lane of the wave (the one caller on the host).
+PT_HD bool wave_any(bool p) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    const float m = __builtin_fabsf(a);
-    if (__builtin_expect(!(m >= 0x1p-126f && m <= 0x1p126f), 0)) return 1.0f / a;
-    const float r = __builtin_amdgcn_rcpf(a);
-    const float e = __builtin_fmaf(-a, r, 1.0f);
-    return __builtin_fmaf(e, r, r);
+    return __builtin_amdgcn_ballot_w64(p) != 0;
 #else
-    return 1.0f / a;
+    return p;
 #endif
 }
 
-PT_HD float sqrt_exact(float x) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    if (__builtin_expect(!(x >= 0x1p-100f && x <= 0x1p100f), 0)) return __builtin_sqrtf(x);
+// The fast sequences themselves, for callers that know the range.
+__device__ __forceinline__ float rcp_newton(float a) {  // == 1.0f / a for |a| in [2^-126, 2^126]
+    const float r = __builtin_amdgcn_rcpf(a);
+    const float e = __builtin_fmaf(-a, r, 1.0f);
+    return __builtin_fmaf(e, r, r);
+}
+__device__ __forceinline__ float sqrt_fixup(float x) {  // == sqrtf(x) for x in [2^-100, 2^100]
     const float s = __builtin_amdgcn_sqrtf(x);
     const float sd = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, s) - 1u);
     const float su = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, s) + 1u);
@@ -80,8 +99,63 @@ PT_HD float sqrt_exact(float x) {
     float r = rd <= 0.0f ? sd : s;
     r = ru > 0.0f ? su : r;
     return r;
+}
+#endif
+
+PT_HD float rcp_exact(float a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const float m = __builtin_fabsf(a);
+    const bool out = !(m >= 0x1p-126f && m <= 0x1p126f);
+#if PT_WAVE_GUARD
+    float f = rcp_newton(a);
+    if (__builtin_expect(wave_any(out), 0)) f = 1.0f / a;
+    return f;
+#else
+    if (__builtin_expect(out, 0)) return 1.0f / a;
+    return rcp_newton(a);
+#endif
+#else
+    return 1.0f / a;
+#endif
+}
+
+PT_HD float sqrt_exact(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const bool out = !(x >= 0x1p-100f && x <= 0x1p100f);
+#if PT_WAVE_GUARD
+    float r = sqrt_fixup(x);
+    if (__builtin_expect(wave_any(out), 0)) r = __builtin_sqrtf(x);
+    return r;
+#else
+    if (__builtin_expect(out, 0)) return __builtin_sqrtf(x);
+    return sqrt_fixup(x);
+#endif
 #else
     return __builtin_sqrtf(x);
+#endif
+}
+
+// inv = 1 / d per component (bvh.h:157): rcp_exact three times with ONE range predicate, so the
+// three v_rcp_f32 and their Newton steps interleave in one block. `live`: the lanes whose result
+// is used; the others' components (a stale or never-set d) neither start the fallback nor get
+// a defined result. kUnit: every live d is a unit vector made by hemisphere_dir, |component| <= 1,
+// so the upper bound cannot fail and only the lower one is tested; callers' rays, and directions
+// that went through a division (the camera's and the specular sampler's normalize, whose length
+// can underflow to 0 and give an infinite component), take the two-sided test.
+// A NaN component beside two in range passes the predicate (v_min3 / v_max3 skip NaN): both
+// sides then give a NaN, possibly of different payload; inv only ever feeds comparisons.
+template <bool kUnit = false>
+PT_HD v3 rcp3_exact(v3 d, bool live = true) {
+#if defined(__HIP_DEVICE_COMPILE__) && PT_WAVE_GUARD
+    const float ax = __builtin_fabsf(d.x), ay = __builtin_fabsf(d.y), az = __builtin_fabsf(d.z);
+    bool out = !(__builtin_fminf(__builtin_fminf(ax, ay), az) >= 0x1p-126f);
+    if (!kUnit) out = out || !(__builtin_fmaxf(__builtin_fmaxf(ax, ay), az) <= 0x1p126f);
+    v3 r{rcp_newton(d.x), rcp_newton(d.y), rcp_newton(d.z)};
+    if (__builtin_expect(wave_any(live && out), 0)) r = v3{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
+    return r;
+#else
+    (void)live;
+    return v3{rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z)};
 #endif
 }
 
@@ -111,7 +185,24 @@ PT_HD float div_by_rcp(float a, float b, float y) {
 // vec3::normalize (linalg.h:149-151) with the three divisions by one reciprocal: exact
 // when |len| and every nonzero |component| lie in [2^-60, 2^60] and no component is 0
 // (div_by_rcp); otherwise the IEEE divisions. Same bits as normalize in every case.
+// The wave-uniform form evaluates one predicate: |a|^2 in [2^-100, 2^100] (sqrt_exact's range)
+// puts len in [2^-50, 2^50] and every |component| <= len (1 + 2^-22) below 2^60, so the smallest
+// |component| >= 2^-60 is all that is left to test; a NaN component makes |a|^2 NaN. One
+// reciprocal then feeds the three quotients, and the wave's slow path is the IEEE square root and
+// divisions.
 PT_HD v3 normalize_fast(v3 a) {
+#if defined(__HIP_DEVICE_COMPILE__) && PT_WAVE_GUARD
+    const float l2 = dot(a, a);
+    const float mn = __builtin_fminf(__builtin_fminf(__builtin_fabsf(a.x), __builtin_fabsf(a.y)), __builtin_fabsf(a.z));
+    const bool out = !(l2 >= 0x1p-100f && l2 <= 0x1p100f && mn >= 0x1p-60f);
+    const float lf = sqrt_fixup(l2), y = rcp_newton(lf);
+    v3 r{div_by_rcp(a.x, lf, y), div_by_rcp(a.y, lf, y), div_by_rcp(a.z, lf, y)};
+    if (__builtin_expect(wave_any(out), 0)) {
+        const float len = __builtin_sqrtf(l2);
+        r = v3{a.x / len, a.y / len, a.z / len};
+    }
+    return r;
+#else
     const float len = sqrt_exact(dot(a, a));
     const float m = __builtin_fminf(__builtin_fminf(__builtin_fabsf(a.x), __builtin_fabsf(a.y)), __builtin_fabsf(a.z));
     const float mx = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(a.x), __builtin_fabsf(a.y)), __builtin_fabsf(a.z));
@@ -120,6 +211,7 @@ PT_HD v3 normalize_fast(v3 a) {
         return v3{div_by_rcp(a.x, len, y), div_by_rcp(a.y, len, y), div_by_rcp(a.z, len, y)};
     }
     return v3{a.x / len, a.y / len, a.z / len};
+#endif
 }
 
 PT_HD float std_max(float a, float b) { return (a < b) ? b : a; }
@@ -141,6 +233,8 @@ PT_HD float std_max3(float a, float b, float c) {
 struct Lcg {
     uint32_t s;
     PT_HD float next01() {
+        // one v_mul_lo_u32: 4.6 cycles per wave-instruction, the cost of any other main-port form
+        // (tools/valu_ubench.hip), so a restatement by 24-bit multiplies has nothing to gain
         s = 1664525u * s + 1013904223u;
         return (float)s * 0x1p-32f;  // == (float)s / 2^32 exactly
     }
@@ -363,7 +457,7 @@ PT_HD float acosf_ref(float x) {
 
 // Device form: the three cases of acosf_ref as one instruction stream (every lane runs
 // the polynomial, both divisions and the sqrt once; the case picks the result), each
-// division as rcp_exact + one Markstein correction (div_by_rcp) and sqrt_exact. Not
+// division as the exact reciprocal + one Markstein correction (div_by_rcp) and the exact sqrt. Not
 // claimed for every (p, q) — but acosf_fast(x) == acosf_ref(x) for EVERY float x in
 // [-1, 1], the whole domain the path reaches (argument 2u - 1, material.h:9), by
 // exhaustive GPU sweep (pt_debug_sweep 2, tests/test_gpu_parity.py). Cases split over a
@@ -375,22 +469,47 @@ PT_HD float acosf_fast(float x) {
     const float q1 = -2.4033949375e+00f, q2 = 2.0209457874e+00f, q3 = -6.8828397989e-01f,
                 q4 = 7.7038154006e-02f;
     const uint32_t ux = f2u(x), ax = ux & 0x7fffffffu;
-    if (__builtin_expect(ax >= 0x3f800000u || ax <= 0x32800000u, 0)) return acosf_ref(x);  // |x| >= 1, tiny
+    const bool edge = ax >= 0x3f800000u || ax <= 0x32800000u;  // |x| >= 1, tiny
+#if !(defined(__HIP_DEVICE_COMPILE__) && PT_ACOS_WAVE)
+    if (__builtin_expect(edge, 0)) return acosf_ref(x);
+#endif
     const bool small = ax < 0x3f000000u;
     // 1 + x for x <= -0.5 and 1 - x for x >= 0.5 are both 1 - |x|
     const float z = small ? x * x : (1.0f - u2f(ax)) * 0.5f;
     const float p = z * (p0 + z * (p1 + z * (p2 + z * (p3 + z * (p4 + z * p5)))));
     const float q = 1.0f + z * (q1 + z * (q2 + z * (q3 + z * q4)));
-    const float r = div_by_rcp(p, q, rcp_exact(q));
     const float zs = small ? 0.25f : z;  // |x| < 0.5 uses neither s nor c
+#if defined(__HIP_DEVICE_COMPILE__) && PT_ACOS_WAVE
+    // No inner guards: for every x with 2^-26 < |x| < 1 the operands stay far inside the fast
+    // sequences' ranges, q in [0.515, 1], zs in [2^-25, 0.25], s + df in [3.4e-4, 1]
+    // (tests/test_exact_guards_cpu.py recomputes them over the sampler's whole grid; the
+    // exhaustive sweep checks the result on every float). The edge inputs run the same stream
+    // (any value, no trap) and, once per wave that holds one, take fdlibm's constants.
+    const float r = div_by_rcp(p, q, rcp_newton(q));
+    const float s = sqrt_fixup(zs);
+#else
+    const float r = div_by_rcp(p, q, rcp_exact(q));
     const float s = sqrt_exact(zs);
+#endif
     const float df = u2f(f2u(s) & 0xfffff000u);
     const float sd = s + df;
+#if defined(__HIP_DEVICE_COMPILE__) && PT_ACOS_WAVE
+    const float c = div_by_rcp(zs - df * df, sd, rcp_newton(sd));
+#else
     const float c = div_by_rcp(zs - df * df, sd, rcp_exact(sd));
+#endif
     const float v_small = pio2_hi - (x - (pio2_lo - x * r));
     const float v_neg = pi - 2.0f * (s + (r * s - pio2_lo));
     const float v_pos = 2.0f * (df + (r * s + c));
-    return small ? v_small : ((ux >> 31) ? v_neg : v_pos);
+    float v = small ? v_small : ((ux >> 31) ? v_neg : v_pos);
+#if defined(__HIP_DEVICE_COMPILE__) && PT_ACOS_WAVE
+    if (__builtin_expect(wave_any(edge), 0)) {
+        if (ax > 0x3f800000u) v = (x - x) / (x - x);
+        else if (ax == 0x3f800000u) v = (ux >> 31) ? pi + 2.0f * pio2_lo : 0.0f;
+        else if (ax <= 0x32800000u) v = pio2_hi + pio2_lo;
+    }
+#endif
+    return v;
 }
 
 // ------------------------------------------------------------------ sincosf (double kernel)
@@ -435,7 +554,7 @@ PT_HD void sincosf_ref(float y, float& sin_out, float& cos_out) {
     }
 }
 
-// Device form: one instruction stream for every |y| >= 2^-12 — the range reduction runs
+// Device form: one instruction stream for every y — the range reduction runs
 // for |y| < pi/4 too, where it yields n = 0 and x unchanged, i.e. the unreduced case —
 // with the double polynomial and the reduction FMA-contracted (glibc's own
 // __sincosf_fma variant does the same on FMA hosts), and the cosine's sign applied to
@@ -444,12 +563,18 @@ PT_HD void sincosf_ref(float y, float& sin_out, float& cos_out) {
 // sincosf_ref for EVERY float in [-2, 7] (theta in [-pi/2, pi/2], phi in [0, 2*pi]),
 // by exhaustive GPU sweep (pt_debug_sweep 3).
 PT_HD void sincosf_fast(float y, float& sin_out, float& cos_out) {
-    const uint32_t t12 = (f2u(y) >> 20) & 0x7ffu;
     const double y0 = (double)y;
     const double rr = y0 * 0x1.45F306DC9C883p+23;  // 2/pi * 2^24
     const int n = ((int32_t)rr + 0x800000) >> 24;
     double x = __builtin_fma(-(double)n, 0x1.921FB54442D18p0, y0);
+#if PT_SINCOS_BITS
+    // The sine polynomial is odd in x and the cosine's even, and rounding is symmetric: the
+    // reduction's sign flip ((n & 3) == 1 or 2: bit 1 of n + 1) goes to the sine's sign bit at the
+    // end instead of a compare and a 64-bit select here.
+    const uint32_t sin_sign = (uint32_t)(__builtin_bit_cast(uint64_t, x) >> 32) ^ (((uint32_t)n + 1u) << 30);
+#else
     if ((n & 3) == 1 || (n & 3) == 2) x = -x;
+#endif
     const double c0 = 0x1p0, c1 = -0x1.ffffffd0c621cp-2, c2 = 0x1.55553e1068f19p-5, c3 = -0x1.6c087e89a359dp-10,
                  c4 = 0x1.99343027bf8c3p-16;
     const double s1c = -0x1.555545995a603p-3, s2c = 0x1.1107605230bc4p-7, s3c = -0x1.994eb3774cf24p-13;
@@ -458,12 +583,25 @@ PT_HD void sincosf_fast(float y, float& sin_out, float& cos_out) {
     const double cc2 = __builtin_fma(x2, c4, c3), ss1 = __builtin_fma(x2, s3c, s2c);
     const double cc1 = __builtin_fma(x2, c1, c0), x5 = x3 * x2, x6 = x4 * x2;
     const double s = __builtin_fma(x3, s1c, x), c = __builtin_fma(x4, c2, cc1);
+#if PT_SINCOS_BITS
+    // The signs by bit field insert: the sine takes the reduced x's sign and the flip (so -0
+    // stays -0, which the sum x3 s1c + x loses), the cosine, positive on |x| <= pi/4, bit 1 of n.
+    // No test for |y| < 2^-12, where glibc returns (y, 1): there n = 0 and the polynomials give
+    // y - y^3/6 and 1 - y^2/2, less than half an ulp from y and from 1 (y^2/6 < 2^-26.5 relative,
+    // y^2/2 < 2^-25), subnormal y included; the exhaustive sweep covers all of them.
+    const float sv = __builtin_copysignf((float)__builtin_fma(x5, ss1, s), u2f(sin_sign));  // v_bfi_b32
+    const float cv = __builtin_copysignf((float)__builtin_fma(x6, cc2, c), u2f((uint32_t)n << 30));
+    const bool swap = (n & 1) != 0;
+    sin_out = swap ? cv : sv;
+    cos_out = swap ? sv : cv;
+#else
     const float sv = (float)__builtin_fma(x5, ss1, s);
     float cv = (float)__builtin_fma(x6, cc2, c);
     if (n & 2) cv = -cv;
-    const bool swap = (n & 1) != 0, tiny = t12 < 0x398u;  // |y| < 2^-12: (y, 1)
+    const bool swap = (n & 1) != 0, tiny = ((f2u(y) >> 20) & 0x7ffu) < 0x398u;  // |y| < 2^-12: (y, 1)
     sin_out = tiny ? y : (swap ? cv : sv);
     cos_out = tiny ? 1.0f : (swap ? sv : cv);
+#endif
 }
 
 // What the path calls: the fast forms on the device, the restatements on the host.

@@ -107,7 +107,7 @@ __device__ __forceinline__ void paths_body(const TraceArgs& A, const PathArgs& P
         float t = 0.0f;
         int hit = -1;
         n_rays += (unsigned long long)__popcll(__ballot(active));
-        const v3 inv{rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z)};  // bvh.h:157
+        const v3 inv = rcp3_exact(d, active);  // bvh.h:157
         const bool fast = !P.force_exact && __all(!active || query_ray_bounded(o, inv));
         if (active)
             hit = fast ? intersect_tree<true>(nodes, tris, stk, tid, o, d, inv, t)

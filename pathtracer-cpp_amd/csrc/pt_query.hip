@@ -151,7 +151,7 @@ __global__ __launch_bounds__(kBlock) void pt_query_kernel(QueryArgs Q) {
             d = v3{Q.dir[3 * i], Q.dir[3 * i + 1], Q.dir[3 * i + 2]};
             if (kAny && Q.tmax) tmax = Q.tmax[i];
         }
-        const v3 inv{rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z)};  // bvh.h:157
+        const v3 inv = rcp3_exact(d, have);  // bvh.h:157
         const bool fast = !Q.force_exact && __all(!have || query_ray_bounded(o, inv));
         float t;
         const int r = query_walk<kAny>(nodes, tris, stk, tid, have, fast, o, d, inv, tmax, t);
@@ -199,7 +199,7 @@ __global__ __launch_bounds__(kBlock) void pt_aov_kernel(TraceArgs A, QueryArgs Q
             Lcg g{0};
             camera_ray(A, q, sample, g, o, d);
         }
-        const v3 inv{rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z)};
+        const v3 inv = rcp3_exact(d, have);
         const bool fast = !Q.force_exact && __all(!have || query_ray_bounded(o, inv));
         float t;
         const int r = query_walk<false>(nodes, tris, stk, tid, have, fast, o, d, inv, 1e30f, t);

@@ -1892,7 +1892,8 @@ __device__ __forceinline__ int shade_inv(const TraceArgs& A, const float4* __res
     rec_cos[k * kBlock + tid] = dot(n, nd);
     o = add(hp, scale(n, 1e-4f));  // SHIFT_BIAS, render.h:16, 52
     d = nd;
-    if constexpr (RejSlab<Rej>::value) inv = v3{rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z)};  // bvh.h:157
+    // bvh.h:157; a hemisphere sample is a unit vector (rcp3_exact), the specular one went through a division
+    if constexpr (RejSlab<Rej>::value) inv = rcp3_exact<!kSpecular>(d);
     if constexpr (Rej::kCompiled) {
         // the next segment (k + 1) is the last and cannot reach an emitter: L stays +0, and k
         // stays too (the record just written is not read: the other lanes' writes issue anyway).
@@ -2185,7 +2186,7 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
 #endif
             next_ray[fresh_tid()] = make_float4(nd.x, nd.y, nd.z, __uint_as_float(gn.s));
             next_at[fresh_tid()] = item;
-            if constexpr (kGenInv) next_inv = v3{rcp_exact(nd.x), rcp_exact(nd.y), rcp_exact(nd.z)};
+            if constexpr (kGenInv) next_inv = rcp3_exact(nd);
         };
         if constexpr (BoxMask::kRayStack) {
             // The shared stock (pt_raystack.h): slots [0, count) hold rays, slot s
@@ -2229,7 +2230,7 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
                     g.s = __float_as_uint(nr.w);
                     d = v3{nr.x, nr.y, nr.z};
                     if constexpr (kGenInv) inv = ti;
-                    else if constexpr (kCarry) inv = v3{rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z)};  // bvh.h:157
+                    else if constexpr (kCarry) inv = rcp3_exact(d);  // bvh.h:157
                     o = v3{A.pos_x, A.pos_y, A.pos_z};
                     k = 0;
                     active = true;
@@ -2263,7 +2264,7 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
                 g.s = __float_as_uint(nr.w);
                 d = v3{nr.x, nr.y, nr.z};
                 if constexpr (kGenInv) inv = next_inv;
-                else if constexpr (kCarry) inv = v3{rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z)};  // bvh.h:157
+                else if constexpr (kCarry) inv = rcp3_exact(d);  // bvh.h:157
                 o = v3{A.pos_x, A.pos_y, A.pos_z};
                 k = 0;
                 active = true;
@@ -2281,7 +2282,7 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
         if (A.depth > 0) n_rays += (unsigned long long)__popcll(__ballot(tr));
         // bvh.h:157 inv = 1 / d. Waves whose lanes all have finite inv take the IEEE
         // min/max slab test (identical result, see slab_hit_finite).
-        if constexpr (!kCarry) inv = v3{rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z)};
+        if constexpr (!kCarry) inv = rcp3_exact(d, tr);
         const bool forced = A.force_exact_slab == 1 || (A.force_exact_slab == 2 && ((tid >> 6) & 1));
         // with the sign-bit box mask (BoxMask::kSignMask) the wave's plane values must stay
         // finite: |1 / d| <= 2^60 and |o| < 2^60 (scene coordinates < 2^60: the host's
@@ -2447,7 +2448,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& A) {
         int hit = -1;
         const bool tr = active && A.depth > 0;
         if (A.depth > 0) n_rays += (unsigned long long)__popcll(__ballot(tr));
-        const v3 inv{rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z)};  // bvh.h:157
+        const v3 inv = rcp3_exact(d, tr);  // bvh.h:157
         const bool forced = A.force_exact_slab == 1 || (A.force_exact_slab == 2 && ((tid >> 6) & 1));
         const bool fast = !forced && __all(!tr || all_finite(inv));
         if (tr) {
@@ -2598,12 +2599,12 @@ __device__ __forceinline__ void trace_body_wide(const TraceArgs& A) {
             best[fresh_tid()] = ~0ull;  // miss; also trace(depth == 0) returns 0 without intersecting (render.h:37)
             done = true;
             if (A.depth > 0) {
-                inv = v3{rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z)};  // bvh.h:157
+                inv = rcp3_exact(d);  // bvh.h:157
 #ifdef PT_EXP_DUP_START  // measurement only: the segment start's 1 / d and range checks once more
                 {
                     v3 d2 = d;
                     asm volatile("" : "+v"(d2.x));
-                    const v3 i2{rcp_exact(d2.x), rcp_exact(d2.y), rcp_exact(d2.z)};
+                    const v3 i2 = rcp3_exact(d2);
                     const float r2 = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(i2.x), __builtin_fabsf(i2.y)),
                                                      __builtin_fabsf(i2.z));
                     asm volatile("" ::"v"(r2), "v"(i2.x), "v"(i2.y), "v"(i2.z));

@@ -24,7 +24,7 @@
 //   fmac, mul, mul_neg (VOP3 for the modifier), min, cndmask_vcc (VOP2), cndmask_sgpr (VOP3),
 //   add_u32, lshl, cmp_sgpr (VOP3 compare to an SGPR pair), sub, add_abs (VOP3), mov_dpp,
 //   fma+add / mul+add / max3+min (two forms alternating), fma_2lanes / fma_4 / fma_16 (EXEC)
-//   mul_lo_u32, mad_u24, mul_u24, lshl_add, cvt_f32_u32, or_sdwa (SDWA word select), perm,
+//   mul_lo_u32, mul_hi_u32, mad_u24, mul_u24, lshl_add, cvt_f32_u32, or_sdwa (SDWA word select), perm,
 //   mul_f64, cvt_f64_f32, max3+mul / fma_mix+mul (a main-port form beside a second-port one)
 // SQ_ACTIVE_INST_VALU2 (rocprofv3) counts the instructions issued on the SIMD's second VALU
 // port: a form that appears there can dual-issue beside a main-port instruction.
@@ -233,6 +233,10 @@ __global__ void __launch_bounds__(256) ubench(float* out, float s) {
             X(a0) M(a1) X(a2) M(a3) X(a4) M(a5) X(a6) M(a7)
 #undef X
 #undef M
+        } else if constexpr (kOp == 46) {  // high half of the 32 x 32 product (fdiv's multiply)
+#define I(x) asm volatile("v_mul_hi_u32 %0, %0, %1" : "+v"(x) : "v"(u7));
+            I(u0) I(u1) I(u2) I(u3) I(u4) I(u5) I(u6) I(u7)
+#undef I
         } else {  // 14..16, 32..34: v_fma_f32 under a partial EXEC mask (the branch is outside the loop)
 #define I(x) asm volatile("v_fma_f32 %0, %0, %1, %1" : "+v"(x) : "v"(s));
             CHAIN8(I)
@@ -294,7 +298,7 @@ int main(int argc, char** argv) {
                       {"add_abs", run<31>},  {"fma_2lanes", run<32>}, {"fma_4", run<33>}, {"fma_16", run<34>},
                       {"mul_lo_u32", run<35>}, {"mad_u24", run<36>}, {"mul_u24", run<37>}, {"lshl_add", run<38>},
                       {"cvt_f32_u32", run<39>}, {"or_sdwa", run<40>}, {"perm", run<41>}, {"mul_f64", run<42>},
-                      {"cvt_f64_f32", run<43>}, {"max3+mul", run<44>}, {"fma_mix+mul", run<45>}};
+                      {"cvt_f64_f32", run<43>}, {"max3+mul", run<44>}, {"fma_mix+mul", run<45>}, {"mul_hi_u32", run<46>}};
     for (const Op& op : ops) {
         bool want = argc <= 2;
         for (int i = 2; i < argc; i++) want = want || strcmp(argv[i], op.name) == 0;
