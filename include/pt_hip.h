@@ -846,10 +846,56 @@ int pt_bvh_trace_grad(const pt_scene* scene, const float* origins, const float* 
  * dropped by `sampled`. The connection at hit k stands for an EMIT hit at k + 1, so it runs for
  * k < depth only and the depth cut is the same. Emission of other materials, unlisted EMIT
  * triangles and everything after a SPECULAR bounce stay with BRDF sampling.
- * Not in this definition: multiple importance sampling (an emitter touching a diffuse surface
- * gives a heavy-tailed 1 / r^2 term), Russian roulette, light sampling at SPECULAR vertices.
+ * Not in this definition: Russian roulette, light sampling at SPECULAR vertices. An emitter that
+ * touches a diffuse surface gives the term of step 4 a heavy 1 / r^2 tail; the weighted estimator
+ * below (PT_NEE_MIS_BALANCE, opt-in) removes it.
  *
- * The per-ray result is pt_ctx_trace's: the float32 sum over samples in order from +0, / spp. */
+ * The per-ray result is pt_ctx_trace's: the float32 sum over samples in order from +0, / spp.
+ *
+ * ---- the weighted estimator (multiple importance sampling, balance heuristic) ----
+ * PT_NEE_MIS_BALANCE combines a vertex's light sample with the EMIT hit of its BRDF sample, which the
+ * estimator above drops. It is steps 1-6 above with the same draws in the same order, so the
+ * geometry, the LCG states, the segment counts, shadow_rays and light_draws of every path are the
+ * unweighted estimator's. sqrtf and / are correctly rounded, each operation rounded on its own as
+ * above. Let hA = 0.5f * kA (A / 2 pi; an exact scaling of kA). Two steps change:
+ *
+ *   Step 4, when the connection is allowed (cx > 0 && cy > 0 && r2 > 0):
+ *        a = cy / r2 (the quotient g already holds), s = sqrtf(r2),
+ *        wl = 1 / (1 + (a * hA) / s),
+ *        and a visible light adds ((T o color_h) o emit_j) * (g * wl), g = ((cx / r2) * a) * kA.
+ *   Step 2, an EMIT hit whose triangle is in the light table while `sampled` is true adds
+ *        L = L + (T o emit) * wb instead of nothing, with
+ *        cyd = fabsf(dot(n_hit, d)), n_hit the hit triangle's unit normal as trace() forms it (not
+ *        faced), d the segment's direction, a = cyd / t, wb = 1 / (1 + t / (a * hA)).
+ *   Every other case of step 2 is unchanged.
+ *
+ * wl = p_l / (p_l + p_b) and wb = p_b / (p_l + p_b) in solid angle: the area density 1 / A is
+ * p_l = s^3 / (A cy) seen from the vertex, and Material::reflected_dir's hemisphere sample is
+ * uniform (sin theta = -(2u - 1) is uniform, and the sample is flipped to the normal's side), so
+ * p_b = 1 / 2 pi and p_b / p_l = a hA / s (step 4), a hA / t (step 2, for a unit d). d is a
+ * hemisphere sample, unit to a few ulps, so for the same point the two weights sum to 1 to about
+ * 1e-7, far below any sampling error; no normalisation is added to make it exact.
+ *   * g * wl <= 2 cx / s <= 2 before rounding (g wl = 2 (cx / r2) q / (1 + q / s) with q = a hA, and
+ *     q / (1 + q / s) < s; cx <= s because n is unit): a direct term is at most
+ *     2 (T o color_h o emit_j) in every scene, and the 1 / r^2 tail is gone.
+ *   * t > 0 and s > 0 wherever the weights are formed. Each weight is 1 / (1 + ratio) and not
+ *     p / (p + p'): s / (s + a hA) is inf / inf = NaN where r2 overflows (a vertex far from a
+ *     light: there g = +0 and the unweighted term is +0), and (a hA) / (t + a hA) is NaN where a hA
+ *     overflows. In the form above an overflowing or vanishing operand gives a weight of +0 or 1:
+ *     r2 = inf gives wl = 1 beside g = +0, a hA = inf gives wl = +0 and wb = 1, a hA = +0 gives
+ *     wb = +0. What remains is g itself overflowing to inf beside wl = +0 (NaN), where the
+ *     unweighted term is already inf.
+ *   * The weights are evaluated whether or not the vertex's own light sample could contribute
+ *     (cx <= 0, or occluded): the densities belong to the techniques, not to the sample drawn.
+ *   * A light that sits in two leaves, or twice in the scene, is weighted as the visibility rule
+ *     of step 4 counts it: by its caller's triangle index, with the table's A. */
+#define PT_NEE_MIS_NONE 0        /* the estimator as first defined: an EMIT hit after a light draw adds nothing */
+#define PT_NEE_MIS_BALANCE 1     /* the weighted estimator */
+typedef struct pt_nee_options {  /* 16 bytes */
+    int32_t mis;                 /* PT_NEE_MIS_*; any other value is PT_E_ARG */
+    int32_t reserved[3];         /* must be 0 */
+} pt_nee_options;
+
 typedef struct pt_nee_stats {    /* 88 bytes */
     pt_trace_stats trace;        /* as pt_ctx_trace fills it; trace.rays counts path AND shadow segments */
     uint64_t shadow_rays;        /* shadow segments walked */
@@ -883,6 +929,19 @@ int pt_ctx_trace_nee(pt_ctx* ctx, const float* origins, const float* dirs, int64
  * ends a running sum, as any render does. is_device covers img_out and the pointers of moments. */
 int pt_ctx_render_nee(pt_ctx* ctx, const pt_camera* cam, const pt_params* params, float* img_out,
                       const pt_moments* moments, int is_device, pt_nee_stats* stats);
+
+/* The three calls above with options: `options` NULL or mis == PT_NEE_MIS_NONE is the call above
+ * (its bits, stats and errors; the three above are these with NULL), PT_NEE_MIS_BALANCE the
+ * weighted estimator. Host and device forms stay bit-identical, and the stats have the same meaning. */
+int pt_bvh_trace_nee_opt(const pt_scene* scene, const float* origins, const float* dirs, int64_t n,
+                         const pt_trace_params* params, float* rgb_out, pt_nee_stats* stats,
+                         const pt_nee_options* options);
+int pt_ctx_trace_nee_opt(pt_ctx* ctx, const float* origins, const float* dirs, int64_t n,
+                         const pt_trace_params* params, float* rgb_out, int is_device, pt_nee_stats* stats,
+                         const pt_nee_options* options);
+int pt_ctx_render_nee_opt(pt_ctx* ctx, const pt_camera* cam, const pt_params* params, float* img_out,
+                          const pt_moments* moments, int is_device, pt_nee_stats* stats,
+                          const pt_nee_options* options);
 
 /* Number of rows of part `part_index` for the given partition. */
 int32_t pt_part_rows(int32_t res_y, int32_t part_index, int32_t part_count, int32_t band_rows);

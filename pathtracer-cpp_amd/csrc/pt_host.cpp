@@ -1114,6 +1114,17 @@ void pt::scene_light_table(const pt_scene* s, LightTable& out) {
     out.kA = run / (float)M_PI;
 }
 
+int pt::nee_options_check(const char* who, const pt_nee_options* opt, int* mis) {
+    *mis = PT_NEE_MIS_NONE;
+    if (!opt) return PT_OK;
+    if (opt->mis != PT_NEE_MIS_NONE && opt->mis != PT_NEE_MIS_BALANCE)
+        return set_error(PT_E_ARG, "%s: options: unknown mis mode %d", who, opt->mis);
+    if (opt->reserved[0] != 0 || opt->reserved[1] != 0 || opt->reserved[2] != 0)
+        return set_error(PT_E_ARG, "%s: options: the reserved words must be 0", who);
+    *mis = opt->mis;
+    return PT_OK;
+}
+
 extern "C" {
 
 int pt_abi_version(void) { return PT_ABI_VERSION; }
@@ -1303,11 +1314,15 @@ int pt_scene_lights(const pt_scene* scene, int32_t* tri_out, float* cdf_out, int
 
 // The light-sampling estimator (pt_hip.h: the definition) for a batch of the caller's rays on the
 // host, with the arithmetic of the kernels (pt_nee.h): pt_bvh_trace's walk for path and shadow
-// segments alike, the path in forward form, and the per-ray sum in sample order.
-int pt_bvh_trace_nee(const pt_scene* scene, const float* origins, const float* dirs, int64_t n, const pt_trace_params* prm,
-                     float* rgb_out, pt_nee_stats* stats) {
+// segments alike, the path in forward form, and the per-ray sum in sample order. opt (NULL: the
+// unweighted estimator) selects the balance-heuristic weights of nee_connect_mis and nee_brdf_weight.
+int pt_bvh_trace_nee_opt(const pt_scene* scene, const float* origins, const float* dirs, int64_t n,
+                         const pt_trace_params* prm, float* rgb_out, pt_nee_stats* stats, const pt_nee_options* opt) {
     const auto t_start = std::chrono::steady_clock::now();
     if (stats) memset(stats, 0, sizeof(*stats));
+    int mis_mode;
+    if (int orc = pt::nee_options_check("pt_bvh_trace_nee", opt, &mis_mode)) return orc;
+    const bool mis = mis_mode == PT_NEE_MIS_BALANCE;
     if (!prm) return set_error(PT_E_ARG, "pt_bvh_trace_nee: params is NULL");
     if (n < 0) return set_error(PT_E_ARG, "pt_bvh_trace_nee: n = %lld is negative", (long long)n);
     if (int prc = trace_params_check("pt_bvh_trace_nee", prm)) return prc;
@@ -1339,7 +1354,14 @@ int pt_bvh_trace_nee(const pt_scene* scene, const float* origins, const float* d
                 const pt_material& m = scene->materials[ti];
                 const v3 emit{m.emit[0], m.emit[1], m.emit[2]};
                 if (m.type == PT_MAT_EMIT) {
-                    if (!(sampled && lt.listed[(size_t)ti])) L = nee_add_emit(L, T, emit);
+                    if (!(sampled && lt.listed[(size_t)ti])) {
+                        L = nee_add_emit(L, T, emit);
+                    } else if (mis) {  // the BRDF sample reached a light: its share of the two techniques
+                        const float* v = scene->verts + 9 * (size_t)ti;
+                        const v3 v1{v[0], v[1], v[2]};
+                        const v3 nh = normalize(cross(sub(v3{v[3], v[4], v[5]}, v1), sub(v3{v[6], v[7], v[8]}, v1)));
+                        L = nee_add_emit_weighted(L, T, emit, nee_brdf_weight(nh, d, t, lt.kA));
+                    }
                     break;
                 }
                 L = nee_add_emit(L, T, emit);
@@ -1362,7 +1384,8 @@ int pt_bvh_trace_nee(const pt_scene* scene, const float* origins, const float* d
                                            v3{G[2].x, G[2].y, G[2].z}, x2, x3);
                     v3 w;
                     float gw;
-                    if (nee_connect(y, no, nrm, v3{G[3].x, G[3].y, G[3].z}, lt.kA, w, gw)) {
+                    const v3 nl{G[3].x, G[3].y, G[3].z};
+                    if (mis ? nee_connect_mis(y, no, nrm, nl, lt.kA, w, gw) : nee_connect(y, no, nrm, nl, lt.kA, w, gw)) {
                         float ts;
                         rays++;
                         shadow++;
@@ -1405,6 +1428,11 @@ int pt_bvh_trace_nee(const pt_scene* scene, const float* origins, const float* d
         return set_error(PT_E_RUNAWAY, "%llu specular rejection loops hit the %d-iteration bound",
                          (unsigned long long)runaway, kSpecularIterBound);
     return PT_OK;
+}
+
+int pt_bvh_trace_nee(const pt_scene* scene, const float* origins, const float* dirs, int64_t n, const pt_trace_params* prm,
+                     float* rgb_out, pt_nee_stats* stats) {
+    return pt_bvh_trace_nee_opt(scene, origins, dirs, n, prm, rgb_out, stats, nullptr);
 }
 
 // Material gradients of trace() on the host (pt_hip.h: the per-path terms): pt_bvh_trace's walk

@@ -208,6 +208,9 @@ struct LightTable {
     float area = 0.0f, kA = 0.0f; // A and A / (float)M_PI; both 0 without lights
 };
 void scene_light_table(const pt_scene* s, LightTable& out);
+// The options of the *_nee_opt entry points (pt_host.cpp): *mis = PT_NEE_MIS_NONE for NULL, else
+// opt->mis; PT_E_ARG for an unknown mode or a reserved word that is not 0.
+int nee_options_check(const char* who, const pt_nee_options* opt, int* mis);
 // The table on a device (pt_kernel.hip uploads it on the first light-sampling call after a scene is set).
 struct NeeLights {
     const float* cdf;
@@ -217,12 +220,13 @@ struct NeeLights {
     int32_t count;
     float area, kA;
 };
-// paths_plan for the light-sampling kernels (no path records); camera: the part's camera rays.
-int nee_plan(bool camera, const QueryScene& sc, size_t lds_usable, int num_cus, int64_t items, WalkPlan& plan);
+// paths_plan for the light-sampling kernels (no path records); camera: the part's camera rays;
+// mis: PT_NEE_MIS_* (the weighted estimator has kernels of its own, and so an occupancy of its own).
+int nee_plan(bool camera, int mis, const QueryScene& sc, size_t lds_usable, int num_cus, int64_t items, WalkPlan& plan);
 // One launch over l.m rays (or, with cam, the first l.m pixels of the part) x l.spp samples from
 // sample s_begin; l.ctr: 6 zeroed u64, [4] shadow segments and [5] light draws added. l.grec is not read.
 int nee_launch(void* stream, const QueryScene& sc, const WalkPlan& plan, const PathsLaunch& l, const NeeLights& lights,
-               int32_t s_begin, const pt_camera* cam, const pt_params* prm, const PartShape* shape);
+               int mis, int32_t s_begin, const pt_camera* cam, const pt_params* prm, const PartShape* shape);
 
 // ---- per-pixel rounds of pt_ctx_render_adaptive (pt_adaptive.hip; the host loop is in pt_kernel.hip) ----
 // All on `stream` (a hipStream_t), device pointers, no synchronisation. Lists hold part-local pixel indices.

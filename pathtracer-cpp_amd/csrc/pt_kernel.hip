@@ -2170,12 +2170,15 @@ int pt_ctx_trace(pt_ctx* c, const float* origins, const float* dirs, int64_t n, 
 }
 
 // The light-sampling estimator along the caller's rays: pt_nee_kernel under the shared loop (no
-// path records; the stats add its own counters).
-int pt_ctx_trace_nee(pt_ctx* c, const float* origins, const float* dirs, int64_t n, const pt_trace_params* prm,
-                     float* rgb_out, int is_device, pt_nee_stats* stats) {
+// path records; the stats add its own counters). opt (NULL: the unweighted estimator) picks the
+// kernel; nothing else of the call depends on it.
+int pt_ctx_trace_nee_opt(pt_ctx* c, const float* origins, const float* dirs, int64_t n, const pt_trace_params* prm,
+                         float* rgb_out, int is_device, pt_nee_stats* stats, const pt_nee_options* opt) {
     const auto t_start = std::chrono::steady_clock::now();
     if (stats) memset(stats, 0, sizeof(*stats));
     static const char who[] = "pt_ctx_trace_nee";
+    int mis;
+    if (int rc = nee_options_check(who, opt, &mis)) return rc;
     if (int rc = caller_rays_check(who, c, prm, nullptr, n)) return rc;
     if (n == 0) return PT_OK;
     if (int rc = caller_rays_ready(who, c, !origins || !dirs || !rgb_out)) return rc;
@@ -2186,11 +2189,16 @@ int pt_ctx_trace_nee(pt_ctx* c, const float* origins, const float* dirs, int64_t
         c, R, stats ? &stats->trace : nullptr,
         [&](int64_t items, WalkPlan& plan) {
             if (int lrc = nee_lights(c, &lights)) return lrc;
-            return nee_plan(false, sc, c->lds_usable, c->num_cus, items, plan);
+            return nee_plan(false, mis, sc, c->lds_usable, c->num_cus, items, plan);
         },
-        [&](const PathsLaunch& l) { return nee_launch(c->stream, sc, R.plan, l, lights, 0, nullptr, nullptr, nullptr); });
+        [&](const PathsLaunch& l) { return nee_launch(c->stream, sc, R.plan, l, lights, mis, 0, nullptr, nullptr, nullptr); });
     if (stats && (rc == PT_OK || rc == PT_E_RUNAWAY)) nee_light_stats(stats, c, R.ctr);
     return rc;
+}
+
+int pt_ctx_trace_nee(pt_ctx* c, const float* origins, const float* dirs, int64_t n, const pt_trace_params* prm,
+                     float* rgb_out, int is_device, pt_nee_stats* stats) {
+    return pt_ctx_trace_nee_opt(c, origins, dirs, n, prm, rgb_out, is_device, stats, nullptr);
 }
 
 // The estimator along the part's own camera rays: pt_nee_cam_kernel fills a dense slab
@@ -2198,10 +2206,12 @@ int pt_ctx_trace_nee(pt_ctx* c, const float* origins, const float* dirs, int64_t
 // in order (pt_accumulate_kernel; with moments pt_accumulate_moments_kernel). Launches are cut over
 // samples: c samples with npix * c < 2^31 records inside the slab budget (PT_NEE_CHUNK, test hook:
 // samples per launch). The sums use the render's buffers, so a running sum ends here.
-int pt_ctx_render_nee(pt_ctx* c, const pt_camera* cam, const pt_params* prm, float* img_out, const pt_moments* mom,
-                      int is_device, pt_nee_stats* stats) {
+int pt_ctx_render_nee_opt(pt_ctx* c, const pt_camera* cam, const pt_params* prm, float* img_out, const pt_moments* mom,
+                          int is_device, pt_nee_stats* stats, const pt_nee_options* opt) {
     const auto t_start = std::chrono::steady_clock::now();
     if (stats) memset(stats, 0, sizeof(*stats));
+    int mis;
+    if (int orc = nee_options_check("pt_ctx_render_nee", opt, &mis)) return orc;
     if (!c || !cam || !prm || !img_out) return set_error(PT_E_ARG, "pt_ctx_render_nee: NULL argument");
     if (prm->spp < 1) return set_error(PT_E_ARG, "pt_ctx_render_nee: spp %d", prm->spp);
     if (!c->have_scene) return set_error(PT_E_ARG, "pt_ctx_render_nee: no scene set");
@@ -2251,7 +2261,7 @@ int pt_ctx_render_nee(pt_ctx* c, const pt_camera* cam, const pt_params* prm, flo
         HIP_TRY(hipGetLastError());
     } else {
         if ((rc = nee_lights(c, &lights))) return rc;
-        if ((rc = nee_plan(true, sc, c->lds_usable, c->num_cus, (int64_t)npix * c_max, plan))) return rc;
+        if ((rc = nee_plan(true, mis, sc, c->lds_usable, c->num_cus, (int64_t)npix * c_max, plan))) return rc;
         if ((rc = ensure(&c->d_tslab, &c->tslab_floats, nval * (size_t)c_max))) return rc;
         if (plan.stack_ints > 0 && (rc = ensure(&c->d_qstack, &c->qstack_ints, plan.stack_ints))) return rc;
         if ((rc = trace_counters(c))) return rc;
@@ -2262,7 +2272,7 @@ int pt_ctx_render_nee(pt_ctx* c, const pt_camera* cam, const pt_params* prm, flo
             l.spp = sc_n;
             HIP_TRY(hipMemsetAsync(c->d_tctr, 0, sizeof(unsigned long long), c->stream));  // work head only
             if ((rc = timer.mark(0, c->stream))) return rc;
-            if ((rc = nee_launch(c->stream, sc, plan, l, lights, s0, cam, prm, &shape))) return rc;
+            if ((rc = nee_launch(c->stream, sc, plan, l, lights, mis, s0, cam, prm, &shape))) return rc;
             if ((rc = timer.mark(1, c->stream))) return rc;
             accumulate(sc_n, s0 == 0 ? 1 : 0, s0 + sc_n == spp ? 1 : 0);
             HIP_TRY(hipGetLastError());
@@ -2283,6 +2293,11 @@ int pt_ctx_render_nee(pt_ctx* c, const pt_camera* cam, const pt_params* prm, flo
         nee_light_stats(stats, c, h_ctr);
     }
     return runaway_result(h_ctr[3]);
+}
+
+int pt_ctx_render_nee(pt_ctx* c, const pt_camera* cam, const pt_params* prm, float* img_out, const pt_moments* mom,
+                      int is_device, pt_nee_stats* stats) {
+    return pt_ctx_render_nee_opt(c, cam, prm, img_out, mom, is_device, stats, nullptr);
 }
 
 // Material gradients of trace() along the caller's rays (pt_grad.hip):

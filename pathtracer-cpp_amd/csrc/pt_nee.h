@@ -48,6 +48,37 @@ PT_HD bool nee_connect(v3 y, v3 o, v3 n, v3 nl, float kA, v3& w, float& g) {
     return true;
 }
 
+// ---- the balance-heuristic weights (PT_NEE_MIS_BALANCE). hA = A / 2 pi is an exact scaling of kA.
+// Both are written as 1 / (1 + ratio of the densities), so an operand that overflows or underflows
+// gives a weight of 0 or 1 and never inf / inf (the header text gives the ranges).
+PT_HD float nee_half_area(float kA) { return 0.5f * kA; }
+
+// nee_connect with the light's weight folded into g: g = (((cx / r2) a) kA) wl, a = cy / r2,
+// s = sqrtf(r2), wl = 1 / (1 + (a hA) / s). Same w and same return value as nee_connect.
+PT_HD bool nee_connect_mis(v3 y, v3 o, v3 n, v3 nl, float kA, v3& w, float& g) {
+    w = sub(y, o);
+    const float cx = dot(n, w);
+    const float cy = __builtin_fabsf(dot(nl, w));
+    const float r2 = dot(w, w);
+    g = 0.0f;
+    if (!(cx > 0.0f && cy > 0.0f && r2 > 0.0f)) return false;
+    const float a = cy / r2;
+    const float s = __builtin_sqrtf(r2);
+    const float wl = 1.0f / (1.0f + (a * nee_half_area(kA)) / s);
+    g = (((cx / r2) * a) * kA) * wl;
+    return true;
+}
+
+// The weight of an EMIT hit at distance t along the unit direction d on a listed triangle of unit
+// normal nh (not faced): a = |nh . d| / t, wb = 1 / (1 + t / (a hA)). t > 0 on a hit.
+PT_HD float nee_brdf_weight(v3 nh, v3 d, float t, float kA) {
+    const float a = __builtin_fabsf(dot(nh, d)) / t;
+    return 1.0f / (1.0f + t / (a * nee_half_area(kA)));
+}
+
+// L += (T o emit) wb (the weighted EMIT hit).
+PT_HD v3 nee_add_emit_weighted(v3 L, v3 T, v3 emit, float wb) { return add(L, scale(mul(T, emit), wb)); }
+
 // What a visible light adds: ((T o color) o emit) g.
 PT_HD v3 nee_direct(v3 T, v3 color, v3 emit, float g) { return scale(mul(mul(T, color), emit), g); }
 

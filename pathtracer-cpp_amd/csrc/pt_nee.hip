@@ -3,6 +3,8 @@
 //
 //   pt_nee_kernel<kLdsScene, kLdsStack>      the caller's buffer of rays (BufferRays, pt_paths.h)
 //   pt_nee_cam_kernel<kLdsScene, kLdsStack>  the part's own camera rays (PartRays)
+//   pt_nee_mis_kernel, pt_nee_mis_cam_kernel the same two with the balance-heuristic weights
+//                                            (PT_NEE_MIS_BALANCE; kMis in shade_nee)
 //
 // The loop is pt_paths.h's one-path-per-lane loop: a work item is (ray or pixel, sample), numbered
 // sample-major, a lane takes its next item by claim_item, and item j's radiance is record j of
@@ -67,7 +69,11 @@ __device__ __forceinline__ v3 f4_xyz(float4 a) { return v3{a.x, a.y, a.z}; }
 // Steps 2-6 of the definition for segment k + 1 of the path, after its BVH::intersect. Returns
 // true when the path ends here. Otherwise T, sampled and o are the next segment's, and the lane's
 // next walk is (o, d): the bounce ray, or (shadow set) the shadow ray, with the bounce direction in
-// `bd`, the light's triangle in `lj` and the term a visible light adds in `C`.
+// `bd`, the light's triangle in `lj` and the term a visible light adds in `C`. kMis: the light's
+// weight is folded into C here, before the shadow walk, and an EMIT hit on a listed triangle after
+// a light draw adds its weighted emission (d is that vertex's hemisphere sample, t its distance), so
+// nothing more than without the weights stays live across intersect_tree.
+template <bool kMis>
 __device__ __forceinline__ bool shade_nee(const TraceArgs& A, const NeeArgs& N, const float4* __restrict__ mats,
                                           const float4* __restrict__ tris, int hit, float t, Lcg& g, v3& o, v3& d, int& k,
                                           v3& T, v3& L, bool& sampled, bool& shadow, v3& bd, v3& C, int& lj, bool& drew) {
@@ -81,6 +87,10 @@ __device__ __forceinline__ bool shade_nee(const TraceArgs& A, const NeeArgs& N, 
         bool add_it = true;
         if (sampled) add_it = N.listed[N.rank_tri[hit]] == 0;
         if (add_it) L = nee_add_emit(L, T, emit);
+        if (kMis && !add_it) {  // the BRDF sample reached a light: its share of the two techniques
+            const float4 th = tris[3 * hit + 2];
+            L = nee_add_emit_weighted(L, T, emit, nee_brdf_weight(v3{th.y, th.z, th.w}, d, t, N.kA));
+        }
         return true;
     }
     L = nee_add_emit(L, T, emit);
@@ -102,7 +112,7 @@ __device__ __forceinline__ bool shade_nee(const TraceArgs& A, const NeeArgs& N, 
         const float4* __restrict__ G = N.lgeom + (size_t)kNeeLightF4 * j;
         const v3 y = nee_point(f4_xyz(G[0]), f4_xyz(G[1]), f4_xyz(G[2]), x2, x3);
         float gw;
-        if (nee_connect(y, no, n, f4_xyz(G[3]), N.kA, w, gw)) {
+        if (kMis ? nee_connect_mis(y, no, n, f4_xyz(G[3]), N.kA, w, gw) : nee_connect(y, no, n, f4_xyz(G[3]), N.kA, w, gw)) {
             want = true;
             C = nee_direct(T, color, f4_xyz(G[4]), gw);
             lj = N.ltri[j];
@@ -138,7 +148,7 @@ __device__ __forceinline__ bool shade_nee(const TraceArgs& A, const NeeArgs& N, 
     return false;
 }
 
-template <class Rays, bool kLdsScene, bool kLdsStack>
+template <class Rays, bool kLdsScene, bool kLdsStack, bool kMis>
 __device__ __forceinline__ void nee_body(const TraceArgs& A, const PathArgs& P, const NeeArgs& N) {
     extern __shared__ float4 lds4[];
     const int tid = threadIdx.x;
@@ -210,7 +220,7 @@ __device__ __forceinline__ void nee_body(const TraceArgs& A, const PathArgs& P, 
                 d = bd;
                 shadow = false;
             } else {
-                end = shade_nee(A, N, mats, tris, hit, t, g, o, d, k, T, L, sampled, shadow, bd, C, lj, drew);
+                end = shade_nee<kMis>(A, N, mats, tris, hit, t, g, o, d, k, T, L, sampled, shadow, bd, C, lj, drew);
             }
         }
         n_draws += (unsigned long long)__popcll(__ballot(drew));
@@ -228,19 +238,36 @@ __device__ __forceinline__ void nee_body(const TraceArgs& A, const PathArgs& P, 
 
 template <bool kLdsScene, bool kLdsStack>
 __global__ __launch_bounds__(kBlock) void pt_nee_kernel(TraceArgs A, PathArgs P, NeeArgs N) {
-    nee_body<BufferRays, kLdsScene, kLdsStack>(A, P, N);
+    nee_body<BufferRays, kLdsScene, kLdsStack, false>(A, P, N);
 }
 
 template <bool kLdsScene, bool kLdsStack>
 __global__ __launch_bounds__(kBlock) void pt_nee_cam_kernel(TraceArgs A, PathArgs P, NeeArgs N) {
-    nee_body<PartRays, kLdsScene, kLdsStack>(A, P, N);
+    nee_body<PartRays, kLdsScene, kLdsStack, false>(A, P, N);
+}
+
+template <bool kLdsScene, bool kLdsStack>
+__global__ __launch_bounds__(kBlock) void pt_nee_mis_kernel(TraceArgs A, PathArgs P, NeeArgs N) {
+    nee_body<BufferRays, kLdsScene, kLdsStack, true>(A, P, N);
+}
+
+template <bool kLdsScene, bool kLdsStack>
+__global__ __launch_bounds__(kBlock) void pt_nee_mis_cam_kernel(TraceArgs A, PathArgs P, NeeArgs N) {
+    nee_body<PartRays, kLdsScene, kLdsStack, true>(A, P, N);
 }
 
 namespace {
 
 using NeeKernel = void (*)(TraceArgs, PathArgs, NeeArgs);
 
-NeeKernel nee_kernel(bool camera, bool lds_scene, bool lds_stack) {
+NeeKernel nee_kernel(bool camera, bool lds_scene, bool lds_stack, int mis) {
+    if (mis == PT_NEE_MIS_BALANCE) {
+        if (camera)
+            return lds_scene ? (lds_stack ? pt_nee_mis_cam_kernel<true, true> : pt_nee_mis_cam_kernel<true, false>)
+                             : (lds_stack ? pt_nee_mis_cam_kernel<false, true> : pt_nee_mis_cam_kernel<false, false>);
+        return lds_scene ? (lds_stack ? pt_nee_mis_kernel<true, true> : pt_nee_mis_kernel<true, false>)
+                         : (lds_stack ? pt_nee_mis_kernel<false, true> : pt_nee_mis_kernel<false, false>);
+    }
     if (camera)
         return lds_scene ? (lds_stack ? pt_nee_cam_kernel<true, true> : pt_nee_cam_kernel<true, false>)
                          : (lds_stack ? pt_nee_cam_kernel<false, true> : pt_nee_cam_kernel<false, false>);
@@ -252,16 +279,17 @@ NeeKernel nee_kernel(bool camera, bool lds_scene, bool lds_stack) {
 
 // Placement and grid by the binary walk's shared rules (pt_launch.h), as paths_plan with no
 // record rows: the stack rows, then nodes, triangles and materials (5 float4 per triangle).
-int nee_plan(bool camera, const QueryScene& sc, size_t lds_usable, int num_cus, int64_t items, WalkPlan& plan) {
+int nee_plan(bool camera, int mis, const QueryScene& sc, size_t lds_usable, int num_cus, int64_t items, WalkPlan& plan) {
     place_walk_hooked(sc.num_nodes, sc.num_tris, sc.tree_depth, 5, 0, lds_usable, true, plan);
-    return walk_grid((const void*)nee_kernel(camera, plan.lds_scene, plan.lds_stack), lds_usable, num_cus, items, plan,
+    return walk_grid((const void*)nee_kernel(camera, plan.lds_scene, plan.lds_stack, mis), lds_usable, num_cus, items, plan,
                      camera ? "light-sampling render" : "light-sampling trace");
 }
 
 int nee_launch(void* stream, const QueryScene& sc, const WalkPlan& plan, const PathsLaunch& l, const NeeLights& lights,
-               int32_t s_begin, const pt_camera* cam, const pt_params* prm, const PartShape* shape) {
+               int mis, int32_t s_begin, const pt_camera* cam, const pt_params* prm, const PartShape* shape) {
     const unsigned long long total = (unsigned long long)l.m * (unsigned long long)l.spp;
     if (l.m <= 0 || l.spp <= 0 || l.depth <= 0 || total >= (1ull << 31) || s_begin < 0 || (cam && (!prm || !shape)) ||
+        (mis != PT_NEE_MIS_NONE && mis != PT_NEE_MIS_BALANCE) ||
         (cam && l.m != shape->npix) || (lights.count > 0 && (!lights.cdf || !lights.tri || !lights.geom || !lights.listed)))
         return set_error(PT_E_ARG, "light-sampling launch of %d rays x %d samples from %d, depth %d", l.m, l.spp, s_begin,
                          l.depth);
@@ -287,7 +315,7 @@ int nee_launch(void* stream, const QueryScene& sc, const WalkPlan& plan, const P
     N.nlights = lights.count;
     N.area = lights.area;
     N.kA = lights.kA;
-    hipLaunchKernelGGL(nee_kernel(cam != nullptr, plan.lds_scene, plan.lds_stack), dim3(grid), dim3(kBlock), plan.lds_bytes,
+    hipLaunchKernelGGL(nee_kernel(cam != nullptr, plan.lds_scene, plan.lds_stack, mis), dim3(grid), dim3(kBlock), plan.lds_bytes,
                        (hipStream_t)stream, A, P, N);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_error(PT_E_HIP, "light-sampling launch failed: %s", hipGetErrorString(e));

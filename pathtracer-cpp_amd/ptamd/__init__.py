@@ -312,12 +312,16 @@ class BVH:
         (n, samples)) or, with states None, at pt_sample_seed(i, s, seed)."""
         return self._trace_host(lib().pt_bvh_trace, _lib.pt_trace_stats, origins, directions, depth, samples, seed, states)
 
-    def trace_nee(self, origins, directions, depth: int, samples: int = 1, seed: int = PT_SEED, states=None):
+    def trace_nee(self, origins, directions, depth: int, samples: int = 1, seed: int = PT_SEED, states=None,
+                  mis: bool = False):
         """The light-sampling estimator (include/pt_hip.h: next-event estimation, the same expected
         value as trace() at every depth) along a batch of rays on the host (pt_bvh_trace_nee; no
         device needed), bit-identical to Renderer.trace_nee. Arguments and result as trace(); the
-        stats also count shadow_rays and light_draws (rays = path and shadow segments together)."""
-        return self._trace_host(lib().pt_bvh_trace_nee, _lib.pt_nee_stats, origins, directions, depth, samples, seed, states)
+        stats also count shadow_rays and light_draws (rays = path and shadow segments together).
+        `mis`: the weighted estimator (PT_NEE_MIS_BALANCE, pt_bvh_trace_nee_opt): the same draws and
+        counts, with the light sample and the BRDF sample's EMIT hit combined by the balance heuristic."""
+        return self._trace_host(_nee_call("pt_bvh_trace_nee", mis), _lib.pt_nee_stats, origins, directions, depth, samples,
+                                seed, states)
 
     def _trace_host(self, fn, stats_type, origins, directions, depth, samples, seed, states):
         ref = _SceneRef(self)
@@ -384,6 +388,15 @@ class _SceneRef:
 
 SCENE_INFO_KEYS = ("nodes", "tree_depth", "flat_leaves", "ref_stack", "wide_nodes", "wide_width", "wide_levels",
                    "wide_top", "wide_tris", "wide_record_bytes")
+
+
+def _nee_call(name: str, mis: bool):
+    """The light-sampling entry point `name`, or with `mis` its *_opt form bound to PT_NEE_MIS_BALANCE."""
+    if not mis:
+        return getattr(lib(), name)
+    fn = getattr(lib(), name + "_opt")
+    opt = _lib.pt_nee_options(_lib.PT_NEE_MIS_BALANCE, (0, 0, 0))
+    return lambda *args: fn(*args, C.byref(opt))
 
 
 def scene_info(bvh: BVH) -> dict:
@@ -709,12 +722,15 @@ class Renderer:
         before they are read."""
         return self._caller_rays(lib().pt_ctx_trace, _lib.pt_trace_stats, origins, directions, depth, samples, seed, states, out)
 
-    def trace_nee(self, origins, directions, depth: int, samples: int = 1, seed: int = PT_SEED, states=None, out=None):
+    def trace_nee(self, origins, directions, depth: int, samples: int = 1, seed: int = PT_SEED, states=None, out=None,
+                  mis: bool = False):
         """The light-sampling estimator (include/pt_hip.h) along a batch of the caller's rays on
         this context's scene (pt_ctx_trace_nee): arguments, numpy and tensor paths as trace(),
         bit-identical to BVH.trace_nee. Tensors follow the rule of the device-pointer paths: on
-        the context's device, and torch's current stream is waited for before they are read."""
-        return self._caller_rays(lib().pt_ctx_trace_nee, _lib.pt_nee_stats, origins, directions, depth, samples, seed, states, out)
+        the context's device, and torch's current stream is waited for before they are read.
+        `mis`: the weighted estimator (PT_NEE_MIS_BALANCE, pt_ctx_trace_nee_opt), as BVH.trace_nee's."""
+        return self._caller_rays(_nee_call("pt_ctx_trace_nee", mis), _lib.pt_nee_stats, origins, directions, depth, samples,
+                                 seed, states, out)
 
     def _device_tensors(self, items, message: str, count_message: Optional[str] = None, dtype=None) -> None:
         """The checks of a tensor path on (tensor, element count or None) pairs: each a contiguous
@@ -750,14 +766,15 @@ class Renderer:
         return rgb, st.as_dict()
 
     def render_nee(self, camera: Camera, samples: int, depth: int, seed: int = PT_SEED, part_index: int = 0,
-                   part_count: int = 1, band_rows: int = 1, out=None, want: Sequence[str] = ()):
+                   part_count: int = 1, band_rows: int = 1, out=None, want: Sequence[str] = (), mis: bool = False):
         """Render this part's rows with the light-sampling estimator (pt_ctx_render_nee) along the
         render's own camera rays: (img, moments, stats). img is the float32 sum of `samples`
         samples per pixel in sample order, divided by `samples`; moments holds the entries of
         `want` ("sum", "sumsq", "sem", as render_moments defines them) over those samples. One
         shot: it cannot be continued, and it ends this context's running sum. `out`: None (numpy
         results) or a torch float32 tensor on this context's device, written in place; the moments
-        are then tensors there."""
+        are then tensors there. `mis`: the weighted estimator (PT_NEE_MIS_BALANCE,
+        pt_ctx_render_nee_opt), as trace_nee's."""
         W, H = camera.res
         rows = self.part_rows(H, part_index, part_count, band_rows)
         prm = _lib.pt_params(samples, depth, seed, part_index, part_count, band_rows, 0, 0)
@@ -765,7 +782,7 @@ class Renderer:
         if dev:
             _own_device_tensors(self.device, out)
         st = _lib.pt_nee_stats()
-        check(lib().pt_ctx_render_nee(self.h, C.byref(camera.c), C.byref(prm), img_ptr, C.byref(mom), dev, C.byref(st)))
+        check(_nee_call("pt_ctx_render_nee", mis)(self.h, C.byref(camera.c), C.byref(prm), img_ptr, C.byref(mom), dev, C.byref(st)))
         return img, res, st.as_dict()
 
     def trace_grad(self, origins, directions, grad_rgb, depth: int, samples: int = 1, seed: int = PT_SEED, states=None,

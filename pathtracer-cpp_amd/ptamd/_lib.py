@@ -37,7 +37,9 @@ EXPORTED = (
     "pt_moments_variance", "pt_ctx_moments_variance", "pt_image_denoise", "pt_ctx_denoise", "pt_ctx_render_denoised",
     "pt_image_temporal", "pt_ctx_temporal", "pt_ctx_render_temporal",
     "pt_scene_lights", "pt_bvh_trace_nee", "pt_ctx_trace_nee", "pt_ctx_render_nee",
+    "pt_bvh_trace_nee_opt", "pt_ctx_trace_nee_opt", "pt_ctx_render_nee_opt",
 )
+PT_NEE_MIS_NONE, PT_NEE_MIS_BALANCE = 0, 1
 PT_MAX_DEVICES = 16
 
 
@@ -139,6 +141,11 @@ class pt_nee_stats(C.Structure):
         d = self.trace.as_dict()
         d.update(shadow_rays=self.shadow_rays, light_draws=self.light_draws, lights=self.lights, light_area=self.light_area)
         return d
+
+
+class pt_nee_options(C.Structure):
+    """Options of the *_nee_opt calls (include/pt_hip.h): mis = PT_NEE_MIS_*, the reserved words 0."""
+    _fields_ = [("mis", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
 class pt_moments(C.Structure):
@@ -252,6 +259,7 @@ class pt_aov(C.Structure):
 
 assert C.sizeof(pt_bvh_node) == 40 and C.sizeof(pt_material) == 32 and C.sizeof(pt_trace_stats) == 64
 assert C.sizeof(pt_nee_stats) == 88
+assert C.sizeof(pt_nee_options) == 16
 assert C.sizeof(pt_denoise_params) == 20 and C.sizeof(pt_denoise_stats) == 96 and C.sizeof(pt_denoise_guides) == 40
 assert C.sizeof(pt_temporal_params) == 16 and C.sizeof(pt_temporal_stats) == 24 and C.sizeof(pt_temporal_history) == 56
 
@@ -392,6 +400,10 @@ def lib() -> C.CDLL:
                                            C.POINTER(pt_nee_stats)]
             L.pt_ctx_render_nee.argtypes = [P, C.POINTER(pt_camera), C.POINTER(pt_params), P, C.POINTER(pt_moments),
                                             C.c_int, C.POINTER(pt_nee_stats)]
+        if hasattr(L, "pt_ctx_trace_nee_opt"):  # absent from older builds used in A/B runs
+            L.pt_bvh_trace_nee_opt.argtypes = L.pt_bvh_trace_nee.argtypes + [C.POINTER(pt_nee_options)]
+            L.pt_ctx_trace_nee_opt.argtypes = L.pt_ctx_trace_nee.argtypes + [C.POINTER(pt_nee_options)]
+            L.pt_ctx_render_nee_opt.argtypes = L.pt_ctx_render_nee.argtypes + [C.POINTER(pt_nee_options)]
         if hasattr(L, "pt_debug_rccl_failover"):  # test hooks (absent from older builds used in A/B runs)
             L.pt_debug_rccl_failover.argtypes = [C.c_int32, C.c_int32, P]
         if hasattr(L, "pt_debug_rtc_cache"):

@@ -13,11 +13,14 @@ depth 5, in one process per scene, for each entry of --spp (default 4 and 1024):
   * shadow segments per path and the segments of each estimator;
   * the mean per-pixel sample variance of both estimators, from the moments (sum, sumsq) of
     render_moments and render_nee: mean over pixels and channels of (Q - S^2 / n) / (n - 1);
-  * variance x time, the figure of merit (lower is better), and the ratio of the two.
+  * variance x time, the figure of merit (lower is better), and the ratio of the two;
+  * with --mis, the same columns for the weighted estimator (render_nee(mis=True), the balance
+    heuristic of DESIGN.md §3.24): wall and kernel ms, shadow segments per path, variance,
+    variance x time, and its time and variance over the unweighted estimator's.
 
 Writes <out>/<scene>.json (default profiles/nee) and prints each as one JSON line.
 
-    python3 scripts/nee_bench.py [--scenes cornell,mcornell,sphere223] [--res 1024] [--spp 4,1024]
+    python3 scripts/nee_bench.py [--scenes cornell,mcornell,sphere223] [--res 1024] [--spp 4,1024] [--mis]
 """
 import argparse
 import json
@@ -62,7 +65,7 @@ def mean_variance(mom, n):
     return float(((Q - S * S / n) / (n - 1)).clamp_min(0).mean().item())
 
 
-def bench_scene(name, res, spps, depth, warmup, reps, reps_long):
+def bench_scene(name, res, spps, depth, warmup, reps, reps_long, mis=False):
     import torch
     import ptamd
     sc = make_scene(name, res)
@@ -101,6 +104,20 @@ def bench_scene(name, res, spps, depth, warmup, reps, reps_long):
             "variance_x_ms": {"render": v_ref * ren_w["median"], "render_nee": v_nee * nee_w["median"],
                               "ratio": (v_nee * nee_w["median"]) / (v_ref * ren_w["median"]) if v_ref else None},
             "nee_over_render_ms": nee_w["median"] / ren_w["median"], "nee_over_trace_ms": nee_w["median"] / tr_w["median"]})
+        if mis:
+            mis_w, mis_k, mis_st = timed(lambda: r.render_nee(cam, spp, depth, seed=1, out=out, mis=True)[2], warmup, n)
+            _, mom_mis, _ = r.render_nee(cam, spp, depth, seed=1, out=out, want=("sum", "sumsq"), mis=True)
+            v_mis = mean_variance(mom_mis, spp)
+            del mom_mis
+            rows[-1].update({
+                "render_nee_mis_ms": mis_w, "render_nee_mis_kernel_ms": mis_k,
+                "mis_shadow_segments_per_path": mis_st["shadow_rays"] / paths,
+                "mis_over_nee_ms": mis_w["median"] / nee_w["median"],
+                "mis_over_nee_kernel_ms": mis_k["median"] / nee_k["median"]})
+            rows[-1]["segments"]["render_nee_mis"] = mis_st["rays"]
+            rows[-1]["sample_variance"].update(render_nee_mis=v_mis, mis_over_nee=v_mis / v_nee if v_nee else None)
+            rows[-1]["variance_x_ms"].update(render_nee_mis=v_mis * mis_w["median"],
+                                             mis_over_nee=(v_mis * mis_w["median"]) / (v_nee * nee_w["median"]) if v_nee else None)
     lights, area = nee_st["lights"], nee_st["light_area"]
     r.close()
     return {"scene": sc.name, "label": name, "tris": len(sc.tris), "res": [res, res], "depth": depth,
@@ -116,12 +133,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=31)
     ap.add_argument("--reps-long", type=int, default=31, help="repetitions of the runs above 64 spp")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "nee"))
+    ap.add_argument("--mis", action="store_true", help="also measure the weighted estimator, render_nee(mis=True)")
+    ap.add_argument("--out", default=None, help="default profiles/nee, with --mis profiles/mis")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "mis" if args.mis else "nee")
     os.makedirs(args.out, exist_ok=True)
     for name in args.scenes.split(","):
         res = bench_scene(name, args.res, [int(s) for s in args.spp.split(",")], args.depth, args.warmup, args.reps,
-                          args.reps_long)
+                          args.reps_long, args.mis)
         with open(os.path.join(args.out, name + ".json"), "w") as f:
             json.dump(res, f, indent=1)
         print(json.dumps(res), flush=True)
