@@ -13,6 +13,11 @@ A member is named "<base>/<family>/<argument>":
   far_camera  the base seen along +z from z = -2^k through a field of view of 600 / 2^k radians:
             camera rays with |o| past 2^60 (k = 61) and 2^64 (k = 66) and |1 / d| near 2^60 that
             still hit the scene (the scaled family reaches such origins only where every ray misses).
+Two more families serve the light-sampling tests only (tests/_edgelights.py; not in MEMBERS):
+  far_light      the base plus one EMIT triangle of side 100 at z = -2^k: shadow segments whose
+                 unnormalised direction has a component near 2^k;
+  far_light_big  the same with z = -2^k and sides 2^(k - 10): an area that absorbs the base's
+                 lights in the table's running sum (k = 30) or overflows and is dropped (k = 62).
 No NaN or infinite vertex: the builder rejects them."""
 from __future__ import annotations
 
@@ -115,6 +120,21 @@ def far_camera(base, k: int):
     return scenes.Scene(f"{base.name}/far_camera/{k}", cam, list(base.tris), list(base.mats))
 
 
+def far_light(base, k: int, side=100.0, family: str = "far_light"):
+    """The base plus one EMIT triangle ((200, 200, z), (200 + side, 200, z), (200, 200 + side, z)),
+    z = -2^k, emission (4, 2, 1): on Cornell that is the open side, so the room sees it."""
+    from ptamd import scenes
+    z = -(2.0 ** k)
+    sc = scenes.Scene(f"{base.name}/{family}/{k}", base.camera, list(base.tris), list(base.mats))
+    sc.add([((200.0, 200.0, z), (200.0 + side, 200.0, z), (200.0, 200.0 + side, z))],
+           scenes.Material.make(scenes.EMIT, 0, (4.0, 2.0, 1.0)))
+    return sc
+
+
+def far_light_big(base, k: int):
+    return far_light(base, k, 2.0 ** (k - 10), "far_light_big")
+
+
 def _members():
     out = []
     for b in BASES:
@@ -151,6 +171,10 @@ def make(member: str, res):
         return doubled(b, arg[0])
     if family == "far_camera":
         return far_camera(b, int(arg[0]))
+    if family == "far_light":
+        return far_light(b, int(arg[0]))
+    if family == "far_light_big":
+        return far_light_big(b, int(arg[0]))
     assert family == "degenerate" and not arg
     return degenerate(b)
 
