@@ -943,6 +943,72 @@ int pt_ctx_render_nee_opt(pt_ctx* ctx, const pt_camera* cam, const pt_params* pa
                           const pt_moments* moments, int is_device, pt_nee_stats* stats,
                           const pt_nee_options* options);
 
+/* ---- material gradients of the light-sampling estimator --------------------------
+ * The path geometry, the light choice (by area) and the balance-heuristic weights depend only on
+ * geometry, roughness and the LCG, so the estimator above (steps 1-6, unweighted or
+ * PT_NEE_MIS_BALANCE) is still a polynomial in color and emit_color, and the derivative below is
+ * exact: no bias, no reparameterisation. The conventions are pt_ctx_trace_grad's: float32, one
+ * rounding per operation, no contraction, `o` the per-channel product, the caller's triangle
+ * indices; csrc/pt_nee.h states the arithmetic once for the host form and the kernel.
+ *
+ * Forward. rgb_out is the forward-form value of steps 1-6 evaluated at the override color / emit.
+ * The light table (membership, cdf, A, kA, geometry) is ALWAYS that of the scene (the context's;
+ * for the host form that of pt_scene_lights(scene)); it is never derived again from the override.
+ * Only the emission of light j is taken from the override row of its triangle. So without
+ * overrides, or with overrides under which pt_scene_lights would return the same table, rgb_out is
+ * bit-identical to pt_ctx_trace_nee_opt; with any other override (a light's emission set to zero,
+ * another EMIT triangle lit) it is the estimator over the scene's table: a consistent polynomial
+ * whose gradient is the one returned, but not the estimator of the overridden scene.
+ *
+ * Per-path quantities. Path (i, s) has bounces k = 0 .. K-1 (non-EMIT hits that went on to the
+ * BRDF draw of step 6) on triangles h_k with cosines c_k, then a terminal. A bounce whose light
+ * draw was visible also has (j_k, g_k): the light's triangle and the scalar step 4 forms, g or
+ * g * wl. The terminal is a miss; a non-EMIT hit on the last allowed segment; or an EMIT hit with
+ * multiplier m: m = 1 when the hit is plain (step 2 adds T o emit), m = wb in the weighted
+ * estimator's changed case, and in the unweighted estimator the hit that `sampled` and the table
+ * drop is called dropped: it adds nothing below and is not counted.
+ * w = grad_rgb[i] / (float)spp; Tw_0 = w, Tw_{k+1} = ((2 Tw_k) o color_{h_k}) * c_k.
+ *
+ * Suffix radiance per unit throughput, backwards: R_K is the terminal's value (emit * m for a
+ * weighted hit, emit for a plain hit and for the last segment's non-EMIT hit, +0 for a miss or a
+ * dropped hit); R_k = (emit_{h_k} + D_k) + ((2 R_{k+1}) o color_{h_k}) * c_k with
+ * D_k = (color_{h_k} o emit_{j_k}) * g_k at a visible light draw; otherwise there is no D_k and
+ * R_k = emit_{h_k} + ((2 R_{k+1}) o color_{h_k}) * c_k, pt_ctx_trace_grad's unwinding.
+ *
+ * Terms, in ascending k and in this order within a bounce:
+ *   1. grad_emit[h_k] += Tw_k;
+ *   2. with a visible light: grad_emit[j_k] += (Tw_k o color_{h_k}) * g_k, then
+ *      grad_color[h_k] += (Tw_k o emit_{j_k}) * g_k;
+ *   3. grad_color[h_k] += ((2 Tw_k) o R_{k+1}) * c_k.
+ * A terminal hit then adds Tw_K * m to grad_emit[h_K] (Tw_K itself for a plain hit and for the last
+ * segment's non-EMIT hit). A light draw that was not visible, or whose connection was not allowed,
+ * adds nothing.
+ *
+ * Sums, `terms` and the degenerate cases are pt_ctx_trace_grad's: each destination is the float64
+ * sum of its float32 terms in any order; n = 1, spp = 1 adds in the order above, bit for bit; a
+ * term counts once for its three channels, only for a requested output, also when it is +-0 (it
+ * is then not added); n == 0 zeroes the gradient outputs, depth 0 every output. */
+typedef struct pt_nee_grad_stats {
+    pt_nee_stats nee;       /* as pt_ctx_trace_nee_opt fills it */
+    uint64_t terms;         /* contributions added to the requested ones of grad_color, grad_emit */
+    double grad_ms;         /* zeroing, gathers, split: everything but the path kernel */
+    int32_t lds_table;      /* 1: per-block gradient table in LDS; 0: global atomics only */
+    int32_t reserved;
+} pt_nee_grad_stats;
+
+/* The terms on the host over the caller's own arrays (no device needed), summed in double in
+ * (ray, sample, k) order; rgb_out as stated above. options NULL = PT_NEE_MIS_NONE. */
+int pt_bvh_trace_nee_grad(const pt_scene* scene, const float* origins, const float* dirs, int64_t n,
+                          const pt_trace_params* params, const pt_trace_grad_io* io,
+                          pt_nee_grad_stats* stats, const pt_nee_options* options);
+/* On the context's scene. Arguments, pointers (is_device covers the rays, params->states and every
+ * pointer in io), launch cuts, PT_E_RUNAWAY and synchronisation as pt_ctx_trace_grad; options as
+ * pt_ctx_trace_nee_opt. Uses buffers of its own: a running sum stays valid, and the override
+ * never reaches the scene or its light table. */
+int pt_ctx_trace_nee_grad(pt_ctx* ctx, const float* origins, const float* dirs, int64_t n,
+                          const pt_trace_params* params, const pt_trace_grad_io* io, int is_device,
+                          pt_nee_grad_stats* stats, const pt_nee_options* options);
+
 /* Number of rows of part `part_index` for the given partition. */
 int32_t pt_part_rows(int32_t res_y, int32_t part_index, int32_t part_count, int32_t band_rows);
 

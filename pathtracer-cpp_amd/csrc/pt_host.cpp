@@ -1569,6 +1569,210 @@ int pt_bvh_trace_grad(const pt_scene* scene, const float* origins, const float* 
     return PT_OK;
 }
 
+// Material gradients of the light-sampling estimator on the host (pt_hip.h: the per-path
+// quantities and terms): pt_bvh_trace_nee_opt's walk with colour and emission taken from the
+// override arrays and the light table from the scene, a record per bounce (triangle, cosine, the
+// visible light's triangle or -1, g), then the suffix pass R and the throughput pass Tw. Terms are
+// added in double in (ray, sample, k) order.
+int pt_bvh_trace_nee_grad(const pt_scene* scene, const float* origins, const float* dirs, int64_t n,
+                          const pt_trace_params* prm, const pt_trace_grad_io* io, pt_nee_grad_stats* stats,
+                          const pt_nee_options* opt) {
+    const auto t_start = std::chrono::steady_clock::now();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    static const char who[] = "pt_bvh_trace_nee_grad";
+    int mis_mode;
+    if (int orc = pt::nee_options_check(who, opt, &mis_mode)) return orc;
+    const bool mis = mis_mode == PT_NEE_MIS_BALANCE;
+    if (!prm) return set_error(PT_E_ARG, "%s: params is NULL", who);
+    if (!io) return set_error(PT_E_ARG, "%s: io is NULL", who);
+    if (n < 0) return set_error(PT_E_ARG, "%s: n = %lld is negative", who, (long long)n);
+    if (int prc = trace_params_check(who, prm)) return prc;
+    PackedScene ps;
+    const int rc = pack_scene(scene, ps);  // pt_scene_validate's checks: the walk cannot leave the arrays
+    if (rc) return rc;
+    const bool want_grad = io->grad_color || io->grad_emit;
+    if (want_grad && !io->grad_rgb && n > 0)
+        return set_error(PT_E_ARG, "%s: grad_rgb is NULL but a gradient is asked for", who);
+    const size_t nt = (size_t)scene->num_tris;
+    if (io->grad_color) std::fill(io->grad_color, io->grad_color + 3 * nt, 0.0);
+    if (io->grad_emit) std::fill(io->grad_emit, io->grad_emit + 3 * nt, 0.0);
+    if (n == 0) return PT_OK;
+    if (!origins || !dirs) return set_error(PT_E_ARG, "%s: NULL argument", who);
+    std::vector<v3> color(nt), emit(nt);
+    for (size_t i = 0; i < nt; i++) {
+        const pt_material& m = scene->materials[i];
+        color[i] = io->color ? v3{io->color[3 * i], io->color[3 * i + 1], io->color[3 * i + 2]}
+                             : v3{m.color[0], m.color[1], m.color[2]};
+        emit[i] = io->emit ? v3{io->emit[3 * i], io->emit[3 * i + 1], io->emit[3 * i + 2]}
+                           : v3{m.emit[0], m.emit[1], m.emit[2]};
+    }
+    LightTable lt;
+    scene_light_table(scene, lt);  // the scene's, never the override's; a light's emission is emit[lt.tri[j]]
+    const int nl = (int)lt.tri.size();
+    std::vector<int32_t> stack;
+    stack.reserve((size_t)ps.stack_size + 1);
+    const int depth = prm->depth, spp = prm->spp;
+    const float fs = (float)spp;
+    int32_t rec_tri[PT_MAX_DEPTH], rec_lj[PT_MAX_DEPTH];
+    float rec_cos[PT_MAX_DEPTH], rec_g[PT_MAX_DEPTH];
+    v3 below[PT_MAX_DEPTH];  // R_{k+1}
+    uint64_t rays = 0, runaway = 0, shadow = 0, draws = 0, terms = 0;
+    auto add3 = [](double* dst, size_t tri, v3 t) {
+        dst[3 * tri] += (double)t.x;
+        dst[3 * tri + 1] += (double)t.y;
+        dst[3 * tri + 2] += (double)t.z;
+    };
+    for (int64_t r = 0; r < n; r++) {
+        float sum[3] = {0.0f, 0.0f, 0.0f};
+        for (int s = 0; s < spp; s++) {
+            Lcg g{prm->states ? prm->states[(size_t)r * spp + s] : pt_sample_seed((uint32_t)r, (uint32_t)s, prm->seed)};
+            v3 o{origins[3 * r], origins[3 * r + 1], origins[3 * r + 2]};
+            v3 d{dirs[3 * r], dirs[3 * r + 1], dirs[3 * r + 2]};
+            v3 T{1.0f, 1.0f, 1.0f}, L{0.0f, 0.0f, 0.0f};
+            bool sampled = false;
+            int K = 0;                   // bounces recorded
+            int end_kind = kNeeEndNone;  // the terminal
+            int32_t end_tri = -1;
+            float end_m = 1.0f;
+            for (int k = 1; k <= depth; k++) {
+                float t;
+                rays++;
+                const int32_t ti = walk_ray(scene, stack, o, d, t);
+                if (ti < 0) break;
+                const pt_material& m = scene->materials[ti];
+                if (m.type == PT_MAT_EMIT) {
+                    end_tri = ti;
+                    if (!(sampled && lt.listed[(size_t)ti])) {
+                        L = nee_add_emit(L, T, emit[ti]);
+                        end_kind = kNeeEndPlain;
+                    } else if (mis) {  // the BRDF sample reached a light: its share of the two techniques
+                        const float* v = scene->verts + 9 * (size_t)ti;
+                        const v3 v1{v[0], v[1], v[2]};
+                        const v3 nh = normalize(cross(sub(v3{v[3], v[4], v[5]}, v1), sub(v3{v[6], v[7], v[8]}, v1)));
+                        end_m = nee_brdf_weight(nh, d, t, lt.kA);
+                        L = nee_add_emit_weighted(L, T, emit[ti], end_m);
+                        end_kind = kNeeEndWeighted;
+                    }
+                    break;
+                }
+                L = nee_add_emit(L, T, emit[ti]);
+                if (k == depth) {  // no light draw at k == depth (step 4), and step 5 ends the path
+                    end_tri = ti;
+                    end_kind = kNeeEndPlain;
+                    break;
+                }
+                const float* v = scene->verts + 9 * (size_t)ti;
+                const v3 v1{v[0], v[1], v[2]};
+                v3 nrm = normalize(cross(sub(v3{v[3], v[4], v[5]}, v1), sub(v3{v[6], v[7], v[8]}, v1)));
+                if (!(dot(nrm, d) < 0.0f)) nrm = neg(nrm);  // triangle.h:48
+                const v3 hp = add(o, scale(d, t));
+                const v3 no = add(hp, scale(nrm, 1e-4f));  // SHIFT_BIAS, render.h:16, 52
+                rec_tri[K] = ti;
+                rec_lj[K] = -1;
+                rec_g[K] = 0.0f;
+                sampled = m.type != PT_MAT_SPECULAR && nl > 0;
+                if (sampled) {
+                    draws++;
+                    const float x1 = g.next01();
+                    const float x2 = g.next01();
+                    const float x3 = g.next01();
+                    const int j = nee_pick(lt.cdf.data(), nl, x1 * lt.area);
+                    const f4* G = lt.geom.data() + (size_t)kNeeLightF4 * j;
+                    const v3 y = nee_point(v3{G[0].x, G[0].y, G[0].z}, v3{G[1].x, G[1].y, G[1].z},
+                                           v3{G[2].x, G[2].y, G[2].z}, x2, x3);
+                    v3 w;
+                    float gw;
+                    const v3 nlj{G[3].x, G[3].y, G[3].z};
+                    if (mis ? nee_connect_mis(y, no, nrm, nlj, lt.kA, w, gw) : nee_connect(y, no, nrm, nlj, lt.kA, w, gw)) {
+                        float ts;
+                        rays++;
+                        shadow++;
+                        if (walk_ray(scene, stack, no, w, ts) == lt.tri[(size_t)j]) {
+                            L = add(L, nee_direct(T, color[ti], emit[(size_t)lt.tri[(size_t)j]], gw));
+                            rec_lj[K] = lt.tri[(size_t)j];
+                            rec_g[K] = gw;
+                        }
+                    }
+                }
+                v3 nd;
+                if (m.type == PT_MAT_SPECULAR) {
+                    if (!specular_dir(g, d, nrm, m.roughness, kSpecularIterBound, nd)) runaway++;
+                } else {
+                    nd = hemisphere_dir(g, nrm);
+                }
+                rec_cos[K] = dot(nrm, nd);
+                T = nee_throughput(T, color[ti], rec_cos[K]);
+                K++;
+                o = no;
+                d = nd;
+            }
+            sum[0] = sum[0] + L.x;  // image.h:27-31
+            sum[1] = sum[1] + L.y;
+            sum[2] = sum[2] + L.z;
+            if (!want_grad) continue;
+            if (io->grad_color) {  // the suffix pass: R_{k+1} below every bounce
+                v3 R = nee_end_value(end_kind, end_tri >= 0 ? emit[(size_t)end_tri] : v3{0.0f, 0.0f, 0.0f}, end_m);
+                for (int j = K - 1; j >= 0; j--) {
+                    const size_t tri = (size_t)rec_tri[j];
+                    below[j] = R;
+                    const bool lit = rec_lj[j] >= 0;
+                    R = nee_suffix(emit[tri], color[tri], rec_cos[j], R, lit, lit ? emit[(size_t)rec_lj[j]] : v3{0.0f, 0.0f, 0.0f},
+                                   rec_g[j]);
+                }
+            }
+            v3 Tw{io->grad_rgb[3 * r] / fs, io->grad_rgb[3 * r + 1] / fs, io->grad_rgb[3 * r + 2] / fs};
+            for (int j = 0; j < K; j++) {
+                const size_t tri = (size_t)rec_tri[j];
+                if (io->grad_emit) {
+                    add3(io->grad_emit, tri, Tw);
+                    terms++;
+                }
+                if (rec_lj[j] >= 0) {
+                    const size_t lj = (size_t)rec_lj[j];
+                    if (io->grad_emit) {
+                        add3(io->grad_emit, lj, nee_pair(Tw, color[tri], rec_g[j]));
+                        terms++;
+                    }
+                    if (io->grad_color) {
+                        add3(io->grad_color, tri, nee_pair(Tw, emit[lj], rec_g[j]));
+                        terms++;
+                    }
+                }
+                if (io->grad_color) {
+                    add3(io->grad_color, tri, nee_throughput(Tw, below[j], rec_cos[j]));
+                    terms++;
+                }
+                Tw = nee_throughput(Tw, color[tri], rec_cos[j]);
+            }
+            if (end_kind != kNeeEndNone && io->grad_emit) {
+                add3(io->grad_emit, (size_t)end_tri, nee_end_term(end_kind, Tw, end_m));
+                terms++;
+            }
+        }
+        if (io->rgb_out) {
+            io->rgb_out[3 * r] = sum[0] / fs;  // image.h:37-40
+            io->rgb_out[3 * r + 1] = sum[1] / fs;
+            io->rgb_out[3 * r + 2] = sum[2] / fs;
+        }
+    }
+    if (stats) {
+        pt_trace_stats& ts = stats->nee.trace;
+        ts.rays = rays;
+        ts.paths = (uint64_t)n * (uint64_t)spp;
+        ts.runaway = runaway;
+        ts.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+        stats->nee.shadow_rays = shadow;
+        stats->nee.light_draws = draws;
+        stats->nee.lights = nl;
+        stats->nee.light_area = lt.area;
+        stats->terms = terms;
+    }
+    if (runaway != 0)
+        return set_error(PT_E_RUNAWAY, "%llu specular rejection loops hit the %d-iteration bound",
+                         (unsigned long long)runaway, kSpecularIterBound);
+    return PT_OK;
+}
+
 // Test hook: FNV-1a (64-bit) of every array and scalar pack_scene produces, so a change to the
 // packing's schedule (threads, order of work) can be checked to leave its output bit-identical.
 int pt_debug_pack_hash(const pt_scene* scene, uint64_t* hash) {

@@ -33,6 +33,7 @@
 #include "pt_hip_debug.h"
 #include "pt_launch.h"
 #include "pt_moments.h"
+#include "pt_nee_grad.h"
 #include "pt_rtc.h"
 #include "pt_trace.h"
 
@@ -440,7 +441,8 @@ struct pt_ctx {
     // material gradients (pt_ctx_trace_grad): pt_ctx_trace's buffers, and
     double* d_gtab = nullptr;                // the gradient table, 6 doubles per caller triangle, then the split outputs
     size_t gtab_doubles = 0;
-    float4* d_gmats = nullptr;               // the per-call materials (override gathered), 2 per packed triangle
+    float4* d_gmats = nullptr;               // the per-call materials (override gathered), 2 per packed triangle; then
+                                             // (pt_ctx_trace_nee_grad) the per-call emission of every light
     size_t gmats_f4 = 0;
     float* d_gbuf = nullptr;                 // staging of a host-pointer call's override rows and grad_rgb
     size_t gbuf_floats = 0;
@@ -2403,6 +2405,125 @@ int pt_ctx_trace_grad(pt_ctx* c, const float* origins, const float* dirs, int64_
         stats->terms = R.ctr[2];
         stats->grad_ms = (double)gather_ms + (double)split_ms;
         stats->lds_table = plan.lds_tab;
+    }
+    return caller_rays_stats(R, ts);
+}
+
+// Material gradients of the light-sampling estimator along the caller's rays (pt_nee_grad.hip,
+// DESIGN.md §3.26): pt_nee_grad_kernel under the shared loop, staged as pt_ctx_trace_grad stages
+// its call. Before the launches the table is zeroed, the per-call materials are gathered (with an
+// override) and so is every light's emission (always: the kernel never reads the light table's
+// own copy); after them the table is split into the caller's two arrays.
+int pt_ctx_trace_nee_grad(pt_ctx* c, const float* origins, const float* dirs, int64_t n, const pt_trace_params* prm,
+                          const pt_trace_grad_io* io, int is_device, pt_nee_grad_stats* stats, const pt_nee_options* opt) {
+    const auto t_start = std::chrono::steady_clock::now();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    static const char who[] = "pt_ctx_trace_nee_grad";
+    int mis;
+    if (int rc = nee_options_check(who, opt, &mis)) return rc;
+    if (int rc = caller_rays_check(who, c, prm, io ? nullptr : "io", n)) return rc;
+    const bool want_grad = io->grad_color || io->grad_emit;
+    if (want_grad && !io->grad_rgb && n > 0)
+        return set_error(PT_E_ARG, "pt_ctx_trace_nee_grad: grad_rgb is NULL but a gradient is asked for");
+    if (int rc = caller_rays_ready(who, c, n > 0 && (!origins || !dirs))) return rc;
+    const int32_t T = c->meta.num_tris;  // the caller's triangles (one tri_idx position each)
+    const size_t g_bytes = 3 * sizeof(double) * (size_t)T;
+    const QueryScene sc = query_scene(c);
+    pt_trace_stats* ts = stats ? &stats->nee.trace : nullptr;
+    NeeGradPlan plan;
+    NeeLights lights;
+    CallerRays R{who, origins, dirs, n, prm, io->rgb_out, is_device, 0, true, t_start};
+    int rc;
+    if (n == 0 || prm->depth == 0)  // no ray is traced: the gradients are +0 as well (caller_rays_begin waits for them)
+        if ((rc = zero_output(c, io->grad_color, g_bytes, is_device)) || (rc = zero_output(c, io->grad_emit, g_bytes, is_device)))
+            return rc;
+    if ((rc = caller_rays_begin(c, R, [&](int64_t items, WalkPlan& walk) {
+            if (int lrc = nee_lights(c, &lights)) return lrc;
+            const int prc = nee_grad_plan(sc, T, c->lds_usable, c->num_cus, prm->depth, items, plan);
+            walk = plan.walk;
+            return prc;
+        })))
+        return rc;
+    if (R.m_max == 0) {
+        if (stats) nee_light_stats(&stats->nee, c, R.ctr);
+        return caller_rays_stats(R, ts);
+    }
+    if ((rc = ensure(&c->d_gtab, &c->gtab_doubles, 12 * (size_t)T))) return rc;  // table, then the split outputs
+    // the per-call materials, then every light's emission
+    if ((rc = ensure(&c->d_gmats, &c->gmats_f4, 2 * (size_t)T + (size_t)lights.count))) return rc;
+    f4* const lemit = reinterpret_cast<f4*>(c->d_gmats) + 2 * (size_t)T;
+    // host pointers: [color 3T][emit 3T][grad_rgb 3 m_max] beside the loop's staging
+    float* s_grgb = nullptr;
+    const float *d_color = io->color, *d_emit = io->emit;
+    if (!is_device) {
+        if ((rc = ensure(&c->d_gbuf, &c->gbuf_floats, 6 * (size_t)T + 3 * (size_t)R.m_max))) return rc;
+        s_grgb = c->d_gbuf + 6 * (size_t)T;
+        if (io->color) {
+            HIP_TRY(hipMemcpyAsync(c->d_gbuf, io->color, 3 * sizeof(float) * (size_t)T, hipMemcpyHostToDevice, c->stream));
+            d_color = c->d_gbuf;
+        }
+        if (io->emit) {
+            HIP_TRY(hipMemcpyAsync(c->d_gbuf + 3 * (size_t)T, io->emit, 3 * sizeof(float) * (size_t)T, hipMemcpyHostToDevice,
+                                   c->stream));
+            d_emit = c->d_gbuf + 3 * (size_t)T;
+        }
+    }
+    EventPair evg, evs;
+    if ((rc = evg.create()) || (rc = evs.create())) return rc;
+    HIP_TRY(hipEventRecord(evg.a, c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_gtab, 0, 6 * sizeof(double) * (size_t)T, c->stream));
+    const f4* mats = sc.mats;
+    if (io->color || io->emit) {
+        if ((rc = grad_gather_mats(c->stream, sc, d_color, d_emit, reinterpret_cast<f4*>(c->d_gmats)))) return rc;
+        mats = reinterpret_cast<const f4*>(c->d_gmats);
+    }
+    if ((rc = nee_grad_gather_lights(c->stream, lights, d_emit, lemit))) return rc;
+    HIP_TRY(hipEventRecord(evg.b, c->stream));
+    NeeGradLaunch gl{};
+    gl.mats = mats;
+    gl.lemit = lemit;
+    gl.table = c->d_gtab;
+    gl.table_rows = T;
+    gl.want_rgb = io->rgb_out ? 1 : 0;
+    gl.want_color = io->grad_color ? 1 : 0;
+    gl.want_emit = io->grad_emit ? 1 : 0;
+    gl.mis = mis;
+    rc = caller_rays_loop(
+        c, R,
+        [&](const PathsLaunch& l) {
+            gl.p = l;
+            return nee_grad_launch(c->stream, sc, plan, gl, lights);
+        },
+        [&](int64_t i0, int32_t m) -> int {
+            gl.grad_rgb = want_grad ? io->grad_rgb + 3 * i0 : nullptr;
+            if (want_grad && !is_device) {
+                HIP_TRY(hipMemcpyAsync(s_grgb, gl.grad_rgb, 3 * sizeof(float) * (size_t)m, hipMemcpyHostToDevice, c->stream));
+                gl.grad_rgb = s_grgb;
+            }
+            return PT_OK;
+        });
+    if (rc) return rc;
+    // the table's rows into the caller's two arrays
+    HIP_TRY(hipEventRecord(evs.a, c->stream));
+    if (want_grad) {
+        double* o_color = io->grad_color ? (is_device ? io->grad_color : c->d_gtab + 6 * (size_t)T) : nullptr;
+        double* o_emit = io->grad_emit ? (is_device ? io->grad_emit : c->d_gtab + 9 * (size_t)T) : nullptr;
+        if ((rc = grad_split_table(c->stream, c->d_gtab, T, o_color, o_emit))) return rc;
+        if (!is_device) {
+            if (o_color) HIP_TRY(hipMemcpyAsync(io->grad_color, o_color, g_bytes, hipMemcpyDeviceToHost, c->stream));
+            if (o_emit) HIP_TRY(hipMemcpyAsync(io->grad_emit, o_emit, g_bytes, hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    HIP_TRY(hipEventRecord(evs.b, c->stream));
+    if ((rc = caller_rays_end(c, R))) return rc;
+    if (stats) {
+        float gather_ms = 0, split_ms = 0;
+        HIP_TRY(hipEventElapsedTime(&gather_ms, evg.a, evg.b));
+        HIP_TRY(hipEventElapsedTime(&split_ms, evs.a, evs.b));
+        stats->terms = R.ctr[2];
+        stats->grad_ms = (double)gather_ms + (double)split_ms;
+        stats->lds_table = plan.lds_tab;
+        nee_light_stats(&stats->nee, c, R.ctr);
     }
     return caller_rays_stats(R, ts);
 }

@@ -88,4 +88,24 @@ PT_HD v3 nee_add_emit(v3 L, v3 T, v3 emit) { return add(L, mul(T, emit)); }
 // The throughput after a bounce with cosine c = n . new_d: T = ((2 T) o color) c.
 PT_HD v3 nee_throughput(v3 T, v3 color, float c) { return scale(mul(scale(T, 2.0f), color), c); }
 
+// ---- the estimator's material gradients (pt_hip.h: "material gradients of the light-sampling
+// estimator"). Two forms carry every term: (a o b) g, and nee_throughput's ((2 a) o b) c, which is
+// also the throughput pass Tw_{k+1} and the colour term ((2 Tw_k) o R_{k+1}) c_k.
+// (a o b) g: D_k = (color o emit_j) g, d emit_j += (Tw o color) g, d color += (Tw o emit_j) g.
+PT_HD v3 nee_pair(v3 a, v3 b, float g) { return scale(mul(a, b), g); }
+
+// R_k from R_{k+1}: (emit + D) + ((2 R) o color) c with a visible light (lit), emit + ... without.
+PT_HD v3 nee_suffix(v3 emit, v3 color, float c, v3 R, bool lit, v3 emit_j, float g) {
+    const v3 e = lit ? add(emit, nee_pair(color, emit_j, g)) : emit;
+    return add(e, nee_throughput(R, color, c));
+}
+
+// The terminal of a path: none (a miss or a dropped hit), a hit with m = 1, a weighted hit.
+enum { kNeeEndNone = 0, kNeeEndPlain = 1, kNeeEndWeighted = 2 };
+// R_K, and what the terminal adds to d emit of its triangle (kind != kNeeEndNone).
+PT_HD v3 nee_end_value(int kind, v3 emit, float m) {
+    return kind == kNeeEndNone ? v3{0.0f, 0.0f, 0.0f} : kind == kNeeEndPlain ? emit : scale(emit, m);
+}
+PT_HD v3 nee_end_term(int kind, v3 Tw, float m) { return kind == kNeeEndWeighted ? scale(Tw, m) : Tw; }
+
 }  // namespace pt

@@ -343,6 +343,18 @@ class BVH:
                                       C.byref(st)))
         return res, st.as_dict()
 
+    def trace_nee_grad(self, origins, directions, grad_rgb, depth: int, samples: int = 1, seed: int = PT_SEED,
+                       states=None, color=None, emit=None, want=GRAD_WANT, mis: bool = False):
+        """Renderer.trace_nee_grad on the host (pt_bvh_trace_nee_grad; no device needed): the same
+        per-path terms, summed in double in (ray, sample, bounce) order."""
+        ref = _SceneRef(self)
+        o, d, n, prm, _st = _host_rays(origins, directions, depth, samples, seed, states)
+        io, res, _keep = _grad_io_host(len(self.triangles), n, grad_rgb, color, emit, want)
+        st = _lib.pt_nee_grad_stats()
+        check(lib().pt_bvh_trace_nee_grad(C.byref(ref.s), o.ctypes.data, d.ctypes.data, n, C.byref(prm), C.byref(io),
+                                          C.byref(st), _nee_options(mis)))
+        return res, st.as_dict()
+
     @classmethod
     def from_scene(cls, scene) -> "BVH":
         b = cls()
@@ -397,6 +409,11 @@ def _nee_call(name: str, mis: bool):
     fn = getattr(lib(), name + "_opt")
     opt = _lib.pt_nee_options(_lib.PT_NEE_MIS_BALANCE, (0, 0, 0))
     return lambda *args: fn(*args, C.byref(opt))
+
+
+def _nee_options(mis: bool):
+    """The options argument of a light-sampling call: NULL, or with `mis` PT_NEE_MIS_BALANCE by reference."""
+    return C.byref(_lib.pt_nee_options(_lib.PT_NEE_MIS_BALANCE, (0, 0, 0))) if mis else None
 
 
 def scene_info(bvh: BVH) -> dict:
@@ -799,7 +816,23 @@ class Renderer:
         the results are tensors there, and the inputs are left untouched. Tensors follow the rule
         of the device-pointer paths: on the context's device, and torch's current stream is waited
         for before they are read."""
-        st = _lib.pt_grad_stats()
+        return self._trace_grad(lib().pt_ctx_trace_grad, _lib.pt_grad_stats(), origins, directions, grad_rgb, depth,
+                                samples, seed, states, color, emit, want)
+
+    def trace_nee_grad(self, origins, directions, grad_rgb, depth: int, samples: int = 1, seed: int = PT_SEED,
+                       states=None, color=None, emit=None, want=GRAD_WANT, mis: bool = False):
+        """trace_grad for the light-sampling estimator (pt_ctx_trace_nee_grad; the definition is in
+        include/pt_hip.h): the radiance Renderer.trace_nee gives at (optionally) changed materials
+        and its exact gradient with respect to them. Arguments, results, numpy and tensor paths are
+        trace_grad's; `mis` is trace_nee's (the weights do not depend on the materials). The light
+        table is always the scene's: an override changes a light's emission, never which
+        triangles are lights. The stats add shadow_rays, light_draws, lights and light_area."""
+        fn = lib().pt_ctx_trace_nee_grad
+        return self._trace_grad(lambda *args: fn(*args, _nee_options(mis)), _lib.pt_nee_grad_stats(), origins, directions,
+                                grad_rgb, depth, samples, seed, states, color, emit, want)
+
+    def _trace_grad(self, fn, st, origins, directions, grad_rgb, depth, samples, seed, states, color, emit, want):
+        """pt_ctx_trace_grad or pt_ctx_trace_nee_grad (`fn`, stats `st`): the tensor path and the numpy path."""
         if _is_tensor(origins):
             import torch
             want = _grad_want(want)
@@ -826,12 +859,12 @@ class Renderer:
                     res[k] = torch.empty((T, 3), dtype=torch.float64, device=origins.device)
                     setattr(io, "grad_" + k, res[k].data_ptr())
             prm = _lib.pt_trace_params(depth, samples, seed, states.data_ptr() if states is not None else None)
-            check(lib().pt_ctx_trace_grad(self.h, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()), n,
-                                          C.byref(prm), C.byref(io), 1, C.byref(st)))
+            check(fn(self.h, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()), n, C.byref(prm), C.byref(io), 1,
+                     C.byref(st)))
             return res, st.as_dict()
         o, d, n, prm, _st = _host_rays(origins, directions, depth, samples, seed, states)
         io, res, _keep = _grad_io_host(self.num_tris, n, grad_rgb, color, emit, want)
-        check(lib().pt_ctx_trace_grad(self.h, o.ctypes.data, d.ctypes.data, n, C.byref(prm), C.byref(io), 0, C.byref(st)))
+        check(fn(self.h, o.ctypes.data, d.ctypes.data, n, C.byref(prm), C.byref(io), 0, C.byref(st)))
         return res, st.as_dict()
 
     def aov(self, camera: Camera, sample: int = 0, seed: int = PT_SEED,

@@ -38,6 +38,7 @@ EXPORTED = (
     "pt_image_temporal", "pt_ctx_temporal", "pt_ctx_render_temporal",
     "pt_scene_lights", "pt_bvh_trace_nee", "pt_ctx_trace_nee", "pt_ctx_render_nee",
     "pt_bvh_trace_nee_opt", "pt_ctx_trace_nee_opt", "pt_ctx_render_nee_opt",
+    "pt_bvh_trace_nee_grad", "pt_ctx_trace_nee_grad",
 )
 PT_NEE_MIS_NONE, PT_NEE_MIS_BALANCE = 0, 1
 PT_MAX_DEVICES = 16
@@ -146,6 +147,17 @@ class pt_nee_stats(C.Structure):
 class pt_nee_options(C.Structure):
     """Options of the *_nee_opt calls (include/pt_hip.h): mis = PT_NEE_MIS_*, the reserved words 0."""
     _fields_ = [("mis", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class pt_nee_grad_stats(C.Structure):
+    """Material gradients of the light-sampling estimator (include/pt_hip.h): pt_nee_stats and pt_grad_stats' own fields."""
+    _fields_ = [("nee", pt_nee_stats), ("terms", C.c_uint64), ("grad_ms", C.c_double), ("lds_table", C.c_int32),
+                ("reserved", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        d = self.nee.as_dict()
+        d.update(terms=self.terms, grad_ms=self.grad_ms, lds_table=self.lds_table)
+        return d
 
 
 class pt_moments(C.Structure):
@@ -260,6 +272,7 @@ class pt_aov(C.Structure):
 assert C.sizeof(pt_bvh_node) == 40 and C.sizeof(pt_material) == 32 and C.sizeof(pt_trace_stats) == 64
 assert C.sizeof(pt_nee_stats) == 88
 assert C.sizeof(pt_nee_options) == 16
+assert C.sizeof(pt_nee_grad_stats) == 112
 assert C.sizeof(pt_denoise_params) == 20 and C.sizeof(pt_denoise_stats) == 96 and C.sizeof(pt_denoise_guides) == 40
 assert C.sizeof(pt_temporal_params) == 16 and C.sizeof(pt_temporal_stats) == 24 and C.sizeof(pt_temporal_history) == 56
 
@@ -404,6 +417,12 @@ def lib() -> C.CDLL:
             L.pt_bvh_trace_nee_opt.argtypes = L.pt_bvh_trace_nee.argtypes + [C.POINTER(pt_nee_options)]
             L.pt_ctx_trace_nee_opt.argtypes = L.pt_ctx_trace_nee.argtypes + [C.POINTER(pt_nee_options)]
             L.pt_ctx_render_nee_opt.argtypes = L.pt_ctx_render_nee.argtypes + [C.POINTER(pt_nee_options)]
+        if hasattr(L, "pt_ctx_trace_nee_grad"):  # absent from older builds used in A/B runs
+            L.pt_bvh_trace_nee_grad.argtypes = [C.POINTER(pt_scene), P, P, C.c_int64, C.POINTER(pt_trace_params),
+                                                C.POINTER(pt_trace_grad_io), C.POINTER(pt_nee_grad_stats),
+                                                C.POINTER(pt_nee_options)]
+            L.pt_ctx_trace_nee_grad.argtypes = [P, P, P, C.c_int64, C.POINTER(pt_trace_params), C.POINTER(pt_trace_grad_io),
+                                                C.c_int, C.POINTER(pt_nee_grad_stats), C.POINTER(pt_nee_options)]
         if hasattr(L, "pt_debug_rccl_failover"):  # test hooks (absent from older builds used in A/B runs)
             L.pt_debug_rccl_failover.argtypes = [C.c_int32, C.c_int32, P]
         if hasattr(L, "pt_debug_rtc_cache"):

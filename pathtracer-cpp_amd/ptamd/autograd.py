@@ -3,7 +3,9 @@
 `trace_radiance(renderer, origins, directions, color, emit, depth, samples, seed)` returns the
 radiance `Renderer.trace` would give on a scene whose triangles carry `color` / `emit`, and its
 backward pass returns the exact gradients with respect to both (Renderer.trace_grad: the paths do
-not depend on either, so the radiance is a polynomial in them). torch is imported on first use.
+not depend on either, so the radiance is a polynomial in them). With `light_sampling` the value is
+`Renderer.trace_nee`'s (the same expectation, a smaller variance) and the backward pass
+Renderer.trace_nee_grad's, exact in the same way. torch is imported on first use.
 """
 from __future__ import annotations
 
@@ -18,11 +20,12 @@ def _function():
 
     class TraceRadiance(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, renderer, origins, directions, color, emit, depth, samples, seed, states):
+        def forward(ctx, renderer, origins, directions, color, emit, depth, samples, seed, states, light_sampling, mis):
             c = None if color is None else color.detach().to(torch.float32).contiguous()
             e = None if emit is None else emit.detach().to(torch.float32).contiguous()
-            res, _ = renderer.trace_grad(origins, directions, None, depth, samples=samples, seed=seed, states=states,
-                                         color=c, emit=e, want=("rgb",))
+            ctx.call = _grad_call(renderer, light_sampling, mis)
+            res, _ = ctx.call(origins, directions, None, depth, samples=samples, seed=seed, states=states,
+                              color=c, emit=e, want=("rgb",))
             ctx.renderer, ctx.rays, ctx.mats = renderer, (origins, directions, states), (c, e)
             ctx.args = (depth, samples, seed)
             ctx.dtypes = (None if color is None else color.dtype, None if emit is None else emit.dtype)
@@ -39,21 +42,34 @@ def _function():
             g_c = g_e = None
             if want:
                 g = grad_rgb.detach().to(torch.float32).contiguous()
-                res, _ = ctx.renderer.trace_grad(origins, directions, g, depth, samples=samples, seed=seed, states=states,
-                                                 color=c, emit=e, want=want)
+                res, _ = ctx.call(origins, directions, g, depth, samples=samples, seed=seed, states=states,
+                                  color=c, emit=e, want=want)
                 if need_c:
                     g_c = res["color"].to(ctx.dtypes[0])
                 if need_e:
                     g_e = res["emit"].to(ctx.dtypes[1])
-            return None, None, None, g_c, g_e, None, None, None, None
+            return None, None, None, g_c, g_e, None, None, None, None, None, None
 
     _fn = TraceRadiance
     return _fn
 
 
-def trace_radiance(renderer, origins, directions, color, emit, depth, samples=1, seed=1, states=None):
+def _grad_call(renderer, light_sampling: bool, mis: bool):
+    """Renderer.trace_grad, or with `light_sampling` Renderer.trace_nee_grad bound to `mis`."""
+    if not light_sampling:
+        if mis:
+            raise ValueError("mis needs light_sampling")
+        return renderer.trace_grad
+    return lambda *args, **kw: renderer.trace_nee_grad(*args, mis=mis, **kw)
+
+
+def trace_radiance(renderer, origins, directions, color, emit, depth, samples=1, seed=1, states=None,
+                   light_sampling=False, mis=False):
     """rgb (n, 3) float32 on the rays' device: trace() along the rays at the given `color` and
     `emit` ((num_tris, 3) tensors on the renderer's device, either may be None = the scene's),
     differentiable with respect to both. origins, directions (and states) are contiguous float32
-    (32-bit integer) tensors on that device, as for Renderer.trace_grad."""
-    return _function().apply(renderer, origins, directions, color, emit, depth, samples, seed, states)
+    (32-bit integer) tensors on that device, as for Renderer.trace_grad. `light_sampling`: the
+    light-sampling estimator (Renderer.trace_nee's value, Renderer.trace_nee_grad's gradients),
+    with `mis` its weighted form; the light table stays the scene's whatever `emit` holds."""
+    return _function().apply(renderer, origins, directions, color, emit, depth, samples, seed, states,
+                             bool(light_sampling), bool(mis))

@@ -27,6 +27,16 @@ same visit. Mray/s = traced segments / the path kernel's time; the table form th
 reported, and where it is the per-block LDS table the global-atomics form (PT_GRAD_LDS=0) is timed
 too, with its atomic bytes per second (8 B per non-zero channel added). The forward values are
 compared bit for bit before anything is timed. Writes <out>/<scene>.json (default profiles/grad).
+
+--mode nee_grad: pt_ctx_trace_nee_grad (rgb and both gradients, device buffers, dLoss/d rgb = 1,
+the weighted estimator) beside pt_ctx_trace_nee_opt and pt_ctx_trace_grad on the same ray set,
+depth and samples (default seeding), timed in turn on the same visit: the wall time of each call,
+--reps times after a warm-up, as its median with the smallest and the largest beside it, and the
+path kernel's time likewise. The forward values are compared bit for bit with trace_nee's before
+anything is timed. Then the variance over --seeds independent seeds (one sample a ray) of d emit
+summed over the light's triangles and of d color of the wall triangle with the largest gradient,
+for trace_nee_grad and for trace_grad, and variance x wall ms of either. Writes <out>/<scene>.json
+(default profiles/nee_grad).
 """
 import argparse
 import json
@@ -263,6 +273,106 @@ def bench_grad_scene(name, res, min_ms, warmup, depth=5):
             "table_form": forms, "min_kernel_ms": min_ms, "device": torch.cuda.get_device_name(0), "lines": lines}
 
 
+def spread(xs):
+    xs = sorted(xs)
+    return {"median": xs[len(xs) // 2] if len(xs) % 2 else 0.5 * (xs[len(xs) // 2 - 1] + xs[len(xs) // 2]), "min": xs[0],
+            "max": xs[-1]}
+
+
+def bench_nee_grad_scene(name, res, warmup, reps, seeds, depth=5, spp=1):
+    import torch
+    import ptamd
+    from ptamd import scenes
+    sc = scenes.cornell((res, res)) if name == "cornell" else scenes.sphere_in_cornell(int(name[len("sphere"):]), (res, res))
+    bvh = ptamd.BVH.from_scene(sc)
+    cam = ptamd.Camera.from_spec(sc.camera)
+    r = ptamd.Renderer(0)
+    r.set_scene(bvh)
+    r.prepare()
+    aov, _ = r.aov(cam, sample=0, channels=("ray",))
+    rays = aov["ray"].reshape(-1, 6)
+    n = rays.shape[0]
+    dev = torch.device("cuda", 0)
+    to = torch.from_numpy(np.ascontiguousarray(rays[:, 0:3])).to(dev)
+    td = torch.from_numpy(np.ascontiguousarray(rays[:, 3:6])).to(dev)
+    tg = torch.ones((n, 3), dtype=torch.float32, device=dev)
+    out = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    last = {}
+
+    def nee_call(seed=1):
+        _, st = r.trace_nee(to, td, depth, samples=spp, seed=seed, out=out, mis=True)
+        last["nee"] = st
+        return st
+
+    def grad_call(seed=1):
+        res_, st = r.trace_grad(to, td, tg, depth, samples=spp, seed=seed)
+        last["grad"], last["grad_res"] = st, res_
+        return st
+
+    def nee_grad_call(seed=1):
+        res_, st = r.trace_nee_grad(to, td, tg, depth, samples=spp, seed=seed, mis=True)
+        last["nee_grad"], last["nee_grad_res"] = st, res_
+        return st
+
+    nee_call()
+    nee_grad_call()
+    assert last["nee"]["rays"] == last["nee_grad"]["rays"] and \
+        torch.equal(out.view(torch.int32), last["nee_grad_res"]["rgb"].view(torch.int32)), \
+        f"{name}: trace_nee and trace_nee_grad forward values differ"
+
+    def timed_wall(call):
+        for _ in range(warmup):
+            call()
+        wall, kern = [], []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            st = call()
+            wall.append((time.perf_counter() - t0) * 1e3)
+            kern.append(st["kernel_ms"])
+        return {"wall_ms": spread(wall), "kernel_ms": spread(kern), "rays_per_call": st["rays"],
+                "mrays_per_s": st["rays"] / spread(kern)["median"] / 1e3}
+
+    lines = {}
+    for _ in range(2):  # in turn, twice: the second round's figures are kept beside the first's
+        for label, call in (("trace_nee", nee_call), ("trace_grad", grad_call), ("trace_nee_grad", nee_grad_call)):
+            lines.setdefault(label, []).append(timed_wall(call))
+    st = last["nee_grad"]
+    for row in lines["trace_nee_grad"]:
+        row.update(terms_per_call=st["terms"], grad_ms_per_call=st["grad_ms"], lds_table=st["lds_table"],
+                   shadow_rays=st["shadow_rays"], light_draws=st["light_draws"])
+    med = {k: spread([row["wall_ms"]["median"] for row in v])["median"] for k, v in lines.items()}
+    ratios = {"nee_grad_over_trace_nee_ms": med["trace_nee_grad"] / med["trace_nee"],
+              "nee_grad_over_trace_grad_ms": med["trace_nee_grad"] / med["trace_grad"]}
+    # variance over independent seeds
+    lights = torch.from_numpy(ptamd.scene_lights(bvh)["tri"].astype(np.int64)).to(dev)
+    grad_call()
+    wall_tri = int(torch.argmax(last["grad_res"]["color"].abs().amax(dim=1)))
+    samples = {"trace_grad": [], "trace_nee_grad": []}
+    for s in range(seeds):
+        grad_call(seed=101 + s)
+        nee_grad_call(seed=101 + s)
+        for label, key in (("trace_grad", "grad_res"), ("trace_nee_grad", "nee_grad_res")):
+            g = last[key]
+            samples[label].append(torch.cat([g["emit"][lights].sum(dim=0), g["color"][wall_tri]]).cpu().numpy())
+    var = {}
+    for label, xs in samples.items():
+        xs = np.stack(xs)
+        var[label] = {"mean_d_emit_light": xs[:, 0:3].mean(axis=0).tolist(), "var_d_emit_light": xs[:, 0:3].var(axis=0, ddof=1).tolist(),
+                      "mean_d_color_wall": xs[:, 3:6].mean(axis=0).tolist(), "var_d_color_wall": xs[:, 3:6].var(axis=0, ddof=1).tolist()}
+    ratio = {}
+    for key in ("var_d_emit_light", "var_d_color_wall"):
+        a, b = np.array(var["trace_nee_grad"][key]), np.array(var["trace_grad"][key])
+        ratio[key] = (a / b).tolist()
+        ratio[key + "_x_ms"] = (a * med["trace_nee_grad"] / (b * med["trace_grad"])).tolist()
+    placement = {k: st[k] for k in ("lds_scene", "lds_stack", "lds_records", "lds_table")}
+    r.close()
+    return {"scene": sc.name, "tris": len(sc.tris), "res": [res, res], "rays": n, "depth": depth, "spp": spp, "mis": True,
+            "placement": placement, "warmup": warmup, "reps": reps, "device": torch.cuda.get_device_name(0), "lines": lines,
+            "wall_ms_median": med, "ratios": ratios,
+            "variance": {"seeds": seeds, "wall_triangle": wall_tri, "lights": int(lights.numel()), "estimators": var,
+                         "nee_grad_over_trace_grad": ratio}}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--scenes", default="cornell,sphere223")
@@ -270,16 +380,21 @@ def main():
     ap.add_argument("--min-ms", type=float, default=1000.0, help="kernel time per line")
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--mode", choices=("query", "trace", "grad"), default="query")
-    ap.add_argument("--out", default=None, help="default profiles/query, profiles/paths with --mode trace, profiles/grad with --mode grad")
+    ap.add_argument("--mode", choices=("query", "trace", "grad", "nee_grad"), default="query")
+    ap.add_argument("--reps", type=int, default=9, help="--mode nee_grad: timed calls per line")
+    ap.add_argument("--seeds", type=int, default=32, help="--mode nee_grad: independent seeds of the variance")
+    ap.add_argument("--out", default=None, help="default profiles/query, profiles/paths with --mode trace, profiles/grad with --mode grad, "
+                    "profiles/nee_grad with --mode nee_grad")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", {"trace": "paths", "grad": "grad"}.get(args.mode, "query"))
+        args.out = os.path.join(ROOT, "profiles", {"trace": "paths", "grad": "grad", "nee_grad": "nee_grad"}.get(args.mode, "query"))
     if args.mode in ("trace", "grad"):
         os.environ["PT_TEST_HOOKS"] = "1"  # PT_FLAT / PT_WIDE pick the yardstick's kernel, PT_GRAD_LDS the table form
     os.makedirs(args.out, exist_ok=True)
     for name in args.scenes.split(","):
-        if args.mode == "grad":
+        if args.mode == "nee_grad":
+            res = bench_nee_grad_scene(name, args.res, args.warmup, args.reps, args.seeds)
+        elif args.mode == "grad":
             res = bench_grad_scene(name, args.res, args.min_ms, args.warmup)
         elif args.mode == "trace":
             res = bench_trace_scene(name, args.res, args.min_ms, args.warmup)
