@@ -122,6 +122,12 @@ int pt_debug_ctx_emit_reject(const pt_ctx* ctx, int32_t* on, float box[6], uint6
  * takes (< 0: none); 4: count after n lanes asked; 5: 1 if the wave is done (flag = a lane is on a
  * path, n = the pool is dry). < 0 on a bad `which`. */
 int pt_debug_ray_stack(int32_t which, int32_t count, int32_t n, int32_t reserve, int32_t flag);
+/* Test hook, no device needed: the dynamic LDS of a flat-kernel block (pt_flatlds.h) for a scene of
+ * num_tris triangles, a box table of box_tab_bytes, pair queues of pair_queue entries per wave and
+ * rec_size path records per lane. out: the byte offsets of [0] triangles [1] materials [2] camera
+ * rows [3] winners [4] camera items [5] box table [6] pair queues [7] record triangles [8] record
+ * cosines, and [9] the block's bytes (what plan_flat asks of the launch). */
+int pt_debug_flat_lds(int32_t num_tris, int32_t box_tab_bytes, int32_t pair_queue, int32_t rec_size, uint32_t out[10]);
 /* Test hook: process-wide counters. which = 0: contexts created (pt_ctx_create), 1: scene
  * uploads (pt_ctx_set_scene), 2: cached multi-device context sets live, 3: uploads skipped
  * because a cached context already held the same scene. */

@@ -478,6 +478,7 @@ struct pt_ctx {
     hipFunction_t rtc_flat = nullptr;        // scene-specialised flat kernel (hipRTC), if built
     std::string rtc_status;                  // why there is no rtc_flat ("" when there is)
     std::string rtc_src;                     // its source while the compile is pending
+    RtcBaked rtc_baked;                      // what that source (pending or loaded) holds as constants
     RtcFuture rtc_job;                       // its pending compile (valid() until taken)
     int64_t last_plan[24] = {};              // pt_debug_ctx_plan: the launch plan of the last render (order: pt_hip_debug.h)
 };
@@ -645,6 +646,8 @@ struct RenderPlan {
     bool use_rtc = false;     // launches run the hipRTC scene kernel (may turn true between launches)
     bool may_switch = false;  // a compile still running may switch this render to it
     int rtc_switch_at = -1;   // PT_RTC_SWITCH_AT (test hook): wait for the compile before launch k
+    int theta_lanes = 0;                // theta_choice's answer, asked once per render
+    const float2* theta_tab = nullptr;
     int blocks_per_cu = 1;
 };
 
@@ -726,13 +729,13 @@ int batch_at(const RenderPlan& P, int s0) {
     return left <= P.batch + P.tail ? left - P.tail : P.batch;
 }
 
-// Dynamic LDS of a flat-kernel block whose waves hold pair queues of `queue` 16-bit entries:
-// triangles and materials (Cornell: 2.5 KB), the queues, the path records, the work-pool words,
-// the prefetched camera rays and the hipRTC kernel's box table.
+// Dynamic LDS of a flat-kernel block whose waves hold pair queues of `queue` 16-bit entries: the
+// layout the kernels form their bases from (pt_flatlds.h) — triangles and materials (Cornell:
+// 2.5 KB), the prefetched camera rays, the winners, the hipRTC kernel's box table, then the
+// queues and the path records.
 size_t flat_lds_bytes(const pt_ctx* c, const RenderPlan& P, int queue) {
-    return sizeof(float4) * (size_t)(3 + 2) * c->meta.num_tris + sizeof(uint16_t) * (size_t)queue * (kBlock / kWave) +
-           (sizeof(uint16_t) + sizeof(float)) * (size_t)kBlock * P.rec + sizeof(unsigned long long) * kBlock +
-           (sizeof(float4) + sizeof(uint32_t)) * kBlock + P.box_tab_bytes;
+    return flat_lds_layout(3u * (unsigned)c->meta.num_tris, 2u * (unsigned)c->meta.num_tris, (unsigned)P.box_tab_bytes,
+                           (unsigned)queue, (unsigned)P.rec).bytes;
 }
 
 // Flat path: (lane, leaf) pair queues of 512 16-bit entries per wave; PT_PAIRS=0
@@ -740,7 +743,7 @@ size_t flat_lds_bytes(const pt_ctx* c, const RenderPlan& P, int queue) {
 void plan_flat(const pt_ctx* c, RenderPlan& P) {
     P.pairs = !hook_off("PT_PAIRS");
     // the hipRTC kernel's box table (box-level pairs), after the prefetched camera rays
-    P.box_tab_bytes = (sizeof(uint16_t) * (size_t)c->flat_boxes + 3) & ~(size_t)3;
+    P.box_tab_bytes = (size_t)rtc_baked(c->meta.num_tris, c->has_specular, c->flat_boxes).box_tab_bytes;
     int queue = P.pairs ? 512 : 0;
     const char* pq = hook_env("PT_PAIR_QUEUE");
     if (P.pairs && pq && *pq) {
@@ -755,7 +758,7 @@ void plan_flat(const pt_ctx* c, RenderPlan& P) {
         const int want = blocks(kPairQueueMin);
         while (queue > kPairQueueMin && blocks(queue) < want) queue -= 32;
     }
-    P.pair_queue = (queue + 3) & ~3;  // keeps the records after the queues 8-B aligned
+    P.pair_queue = (queue + 3) & ~3;  // keeps the records after the queues 8-B aligned (pt_flatlds.h)
     P.lds_scene = true;
     P.lds_bytes = flat_lds_bytes(c, P, P.pair_queue);
 }
@@ -813,6 +816,8 @@ void plan_tree(const pt_ctx* c, RenderPlan& P) {
     P.lds_bytes = work + (P.lds_scene ? scene : 0);
 }
 
+int theta_choice(pt_ctx* c, int* lanes, const float2** tab);  // below
+
 // Everything a render decides before it allocates or launches: batch, kernel family, LDS
 // layout, kernel and blocks per CU.
 int plan_render(pt_ctx* c, const PartShape& shape, const pt_params* prm, int s_lo, int spp, bool moments, RenderPlan& P) {
@@ -844,6 +849,24 @@ int plan_render(pt_ctx* c, const PartShape& shape, const pt_params* prm, int s_l
     const bool rtc_switch = !hook_off("PT_RTC_SWITCH");
     P.rtc_switch_at = hook_int("PT_RTC_SWITCH_AT", -1);
     if (P.flat && c->rtc_job.valid()) rtc_resolve(c, !rtc_switch && (double)shape.npix * (spp - s_lo) >= kRtcWaitPaths);
+    // The scene kernel holds what pt_ctx_set_scene fixed as constants (RtcBaked). Test hooks read at
+    // the render, or a theta table that could not be allocated, can leave this plan with other
+    // values: that kernel is then never launched. The render starts on the table kernel, as it does
+    // while a compile is pending, and a compile of the source with the plan's values is requested.
+    if ((rc = theta_choice(c, &P.theta_lanes, &P.theta_tab))) return rc;
+    if (P.flat && c->rtc_requested) {
+        RtcBaked want = rtc_baked(c->meta.num_tris, c->has_specular, c->flat_boxes);
+        want.theta_lanes = P.theta_lanes;
+        want.pairs = P.pairs;
+        if (!c->rtc_baked.runs(want)) {
+            c->rtc_flat = nullptr;
+            c->rtc_baked = want;
+            c->rtc_src = rtc_flat_source(c->flat_host, c->meta.num_leaves, c->has_specular, c->meta.coords_small, c->albedo_x2,
+                                         c->dark, c->emit, want);
+            c->rtc_job = rtc_job(c->rtc_src);
+            c->rtc_status = "compiling";
+        }
+    }
     P.kern = P.flat        ? (c->flat_fast                    ? (TraceKernel)c->flat_fast
                               : ray_stack_on(c->has_specular) ? pt_trace_kernel<true, true>
                                                               : pt_trace_kernel<true, true, 0, kWideByte, false>)
@@ -888,7 +911,7 @@ int theta_choice(pt_ctx* c, int* lanes, const float2** tab) {
     *lanes = 0;
     *tab = nullptr;
 #if PT_THETA_TAB
-    *lanes = hook_int("PT_THETA_LANES", c->has_specular ? 32 : 0);
+    *lanes = theta_lanes_wanted(c->has_specular);
     if (PT_THETA_TAB == 1 || *lanes > 0) {
         if (int rc = theta_table(c, tab)) {
             if (PT_THETA_TAB == 1) return rc;
@@ -942,9 +965,8 @@ int fill_trace_args(pt_ctx* c, const RenderPlan& P, const pt_camera* cam, const 
         A.flat = c->flat_tab;
     }
     A.radiance = c->d_radiance;
-    const float2* theta_tab = nullptr;
-    if (int rc = theta_choice(c, &A.theta_lanes, &theta_tab)) return rc;
-    A.theta_tab = theta_tab;
+    A.theta_lanes = P.theta_lanes;
+    A.theta_tab = P.theta_tab;
     A.work = c->d_ctr;
     A.ctr = c->d_ctr;
     A.dark = c->dark ? 1 : 0;
@@ -1501,8 +1523,10 @@ int pt_ctx_set_scene(pt_ctx* c, const pt_scene* scene) {
     const bool want_rtc = flat_eligible(ps) && !hook_off("PT_RTC");
     std::string src;
     RtcFuture job;
+    RtcBaked baked;
     if (want_rtc) {
-        src = rtc_flat_source(ps.leaves, ps.num_leaves, specular, ps.coords_small, albedo_x2, dark, emit);
+        baked = rtc_baked(ps.num_tris, specular, flat_box_pairs(ps.leaves, ps.num_leaves));
+        src = rtc_flat_source(ps.leaves, ps.num_leaves, specular, ps.coords_small, albedo_x2, dark, emit, baked);
         job = rtc_job(src);
     }
     if ((rc = ctx_ready(c))) return rc;
@@ -1579,6 +1603,7 @@ int pt_ctx_set_scene(pt_ctx* c, const pt_scene* scene) {
     c->rtc_status = "not a flat scene";
     if (want_rtc) {
         c->rtc_src = std::move(src);
+        c->rtc_baked = baked;
         c->albedo_x2 = albedo_x2;
         c->rtc_requested = true;
         c->flat_boxes = flat_box_pairs(c->flat_host, ps.num_leaves);
@@ -2884,6 +2909,17 @@ int pt_debug_ray_stack(int32_t which, int32_t count, int32_t n, int32_t reserve,
         case 5: return ray_stack_done(flag != 0, count, n != 0) ? 1 : 0;
     }
     return set_error(PT_E_ARG, "pt_debug_ray_stack: which = %d", which);
+}
+
+// Test hook (no device needed): the flat block's LDS layout (pt_flatlds.h), as plan_flat sizes it.
+int pt_debug_flat_lds(int32_t num_tris, int32_t box_tab_bytes, int32_t pair_queue, int32_t rec_size, uint32_t out[10]) {
+    if (!out || num_tris < 0 || box_tab_bytes < 0 || pair_queue < 0 || rec_size < 0)
+        return set_error(PT_E_ARG, "pt_debug_flat_lds: bad argument");
+    const FlatLds l = flat_lds_layout(3u * (unsigned)num_tris, 2u * (unsigned)num_tris, (unsigned)box_tab_bytes,
+                                      (unsigned)pair_queue, (unsigned)rec_size);
+    const uint32_t v[10] = {l.tris, l.mats, l.next_ray, l.best, l.next_at, l.boxtab, l.queues, l.rec_tri, l.rec_cos, l.bytes};
+    memcpy(out, v, sizeof(v));
+    return PT_OK;
 }
 
 // Test hook: the launch plan of the context's last render (pt_hip_debug.h).

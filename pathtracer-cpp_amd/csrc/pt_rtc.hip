@@ -42,10 +42,12 @@ extern char** environ;
 #include "pt_sha256.h"
 #include "pt_trace.h"
 
-// Sources of pt_trace.h, pt_math.h, pt_raystack.h and pt_hip.h, embedded at build time (build/pt_rtc_blob.cpp).
+// Sources of pt_trace.h, pt_math.h, pt_raystack.h, pt_flatlds.h and pt_hip.h, embedded at build time
+// (build/pt_rtc_blob.cpp).
 extern "C" const char* pt_rtc_src_trace;
 extern "C" const char* pt_rtc_src_math;
 extern "C" const char* pt_rtc_src_stack;
+extern "C" const char* pt_rtc_src_lds;
 extern "C" const char* pt_rtc_src_hip;
 
 namespace pt {
@@ -115,7 +117,7 @@ namespace {
 // plane (c - o) * inv is computed once, boxes shared by several leaves are tested once,
 // and a flat axis (lb == rt) needs no min/max. Same IEEE operations as slab_hit_finite.
 std::string flat_mask_source(const std::vector<f4>& leaves, int n, bool specular, bool tri_fast, bool albedo_x2,
-                             bool dark, const EmitBox& emit) {
+                             bool dark, const EmitBox& emit, const RtcBaked& baked) {
     std::vector<std::map<uint32_t, int>> planes(3);
     auto plane = [&](int ax, float c) {
         auto it = planes[ax].find(f2u(c));
@@ -308,6 +310,11 @@ std::string flat_mask_source(const std::vector<f4>& leaves, int n, bool specular
            ";\n    static constexpr bool kTriFast = " + (tri_fast ? "true" : "false") +
            ";\n    static constexpr bool kAlbedoX2 = " + (albedo_x2 ? "true" : "false") +
            ";\n    static constexpr bool kDarkKnown = true;\n    static constexpr bool kDark = " + (dark ? "true" : "false") +
+           // what pt_ctx_set_scene fixes (BakedConsts, pt_trace.h), under PT_KCONST
+           ";\n    static constexpr bool kBaked = PT_KCONST != 0;\n    static constexpr int kNumTri4 = " +
+           std::to_string(baked.num_tri4) + ", kNumMat4 = " + std::to_string(baked.num_mat4) +
+           ", kBoxTabBytes = " + std::to_string(baked.box_tab_bytes) + ", kThetaLanes = " + std::to_string(baked.theta_lanes) +
+           ";\n    static constexpr bool kPairs = " + (baked.pairs ? "true" : "false") +
            ";\n" + rej + "    __device__ __forceinline__ static unsigned long long "
            "mask(const TraceArgs&, v3 o, v3 inv) {\n" +
            body + tests + acc + "        return m;\n    }\n};\n}  // namespace pt\n";
@@ -363,8 +370,38 @@ std::vector<std::string> rtc_extra_flags() {
 
 }  // namespace
 
+// PT_KCONST (default 1; PT_RTC_DEFINES="PT_KCONST=0" is the A/B hook): whether the generated
+// source holds RtcBaked's values as constants.
+bool rtc_kconst_on() {
+    const std::string d = rtc_defines(), key = "#define PT_KCONST ";
+    const size_t at = d.rfind(key);  // the source tests PT_KCONST != 0: so does this
+    return at == std::string::npos || strtol(d.c_str() + at + key.size(), nullptr, 0) != 0;
+}
+
+// theta_choice's lane bound before the table is asked for (pt_kernel.hip): PT_THETA_LANES (tuning
+// hook) or 32 in scenes with a SPECULAR material, else 0; 0 in builds without the table.
+int theta_lanes_wanted(bool specular) {
+#if PT_THETA_TAB
+    return hook_int("PT_THETA_LANES", specular ? 32 : 0);
+#else
+    (void)specular;
+    return 0;
+#endif
+}
+
+RtcBaked rtc_baked(int num_tris, bool specular, int flat_boxes) {
+    RtcBaked k;
+    k.on = rtc_kconst_on();
+    k.num_tri4 = 3 * num_tris;
+    k.num_mat4 = 2 * num_tris;
+    k.box_tab_bytes = (int)flat_box_tab_bytes((unsigned)flat_boxes);
+    k.pairs = !hook_off("PT_PAIRS");
+    k.theta_lanes = theta_lanes_wanted(specular);
+    return k;
+}
+
 std::string rtc_flat_source(const std::vector<f4>& leaves, int n, bool specular, bool tri_fast, bool albedo_x2,
-                            bool dark, const EmitBox& emit) {
+                            bool dark, const EmitBox& emit, const RtcBaked& baked) {
     std::string fl = "// extra flags:";
     for (const std::string& f : rtc_extra_flags()) fl += " " + f;
     // camera fields from the kernel's argument registers at 8 waves: +0.5-1.0 % on configs
@@ -375,14 +412,14 @@ std::string rtc_flat_source(const std::vector<f4>& leaves, int n, bool specular,
     return fl + "\n" + rtc_defines() + (emit.on && emit.sign_only ? "#define PT_EMIT_SIGN_ONLY 1\n" : "") +
            (ray_stack_on(specular) ? "#define PT_RAY_RESERVE " + std::to_string(ray_reserve()) + "\n" : "#define PT_RAY_STACK 0\n") +
            "#define PT_WAVES " + std::to_string(rtc_waves()) +
-           "\n#define PT_FLAT_ONLY 1\n#ifndef PT_CAM_KERNARG\n#define PT_CAM_KERNARG 0\n#endif\n"
+           "\n#define PT_FLAT_ONLY 1\n#ifndef PT_KCONST\n#define PT_KCONST 1\n#endif\n#ifndef PT_CAM_KERNARG\n#define PT_CAM_KERNARG 0\n#endif\n"
            "#ifndef PT_FRESH_TID\n#define PT_FRESH_TID " + (specular ? "1" : "0") + "\n#endif\n"
            "typedef __hip_internal::int32_t int32_t; typedef __hip_internal::uint32_t uint32_t;\n"
            "typedef __hip_internal::int64_t int64_t; typedef __hip_internal::uint64_t uint64_t;\n"
            "typedef __hip_internal::uint8_t uint8_t; typedef __hip_internal::uint16_t uint16_t;\n"
            "#if !defined(__HIP_DEVICE_COMPILE__)\n#error expected a device compilation (pt_math.h fast paths)\n#endif\n"
            "#include \"pt_trace.h\"\n" +
-           flat_mask_source(leaves, n, specular, tri_fast, albedo_x2, dark, emit) +
+           flat_mask_source(leaves, n, specular, tri_fast, albedo_x2, dark, emit, baked) +
            "extern \"C\" __global__ __launch_bounds__(256, PT_WAVES) void pt_trace_flat_rtc(pt::TraceArgs A) {\n"
            "    pt::trace_body_flat<pt::SceneBoxMask>(A);\n}\n";
 }
@@ -468,7 +505,8 @@ std::string rtc_key(const std::string& src) {
     Sha256 k;
     k.update("pathtracer-amd hipRTC code object v1");
     k.update(src.c_str(), src.size() + 1);
-    for (const char* h : {pt_rtc_src_trace, pt_rtc_src_math, pt_rtc_src_stack, pt_rtc_src_hip}) k.update(h, strlen(h) + 1);
+    for (const char* h : {pt_rtc_src_trace, pt_rtc_src_math, pt_rtc_src_stack, pt_rtc_src_lds, pt_rtc_src_hip})
+        k.update(h, strlen(h) + 1);
     for (const std::string& f : rtc_flags()) k.update(f.c_str(), f.size() + 1);
     int maj = 0, mnr = 0;
     (void)hiprtcVersion(&maj, &mnr);
@@ -700,12 +738,12 @@ bool rtc_server_compile(const std::string& src, RtcCode& out) {
         const uint64_t len = n;
         return put(&len, 8) && put(str, n);
     };
-    const char* hdrs[] = {pt_rtc_src_trace, pt_rtc_src_math, pt_rtc_src_stack, pt_rtc_src_hip};
-    const char* names[] = {"pt_trace.h", "pt_math.h", "pt_raystack.h", "pt_hip.h"};
+    const char* hdrs[] = {pt_rtc_src_trace, pt_rtc_src_math, pt_rtc_src_stack, pt_rtc_src_lds, pt_rtc_src_hip};
+    const char* names[] = {"pt_trace.h", "pt_math.h", "pt_raystack.h", "pt_flatlds.h", "pt_hip.h"};
     const std::vector<std::string> flags = rtc_flags();
-    const uint32_t head[3] = {0x51525450u /* "PTRQ" */, 4u, (uint32_t)flags.size()};
+    const uint32_t head[3] = {0x51525450u /* "PTRQ" */, 5u, (uint32_t)flags.size()};
     bool ok = put(head, 12) && put_str(src.data(), src.size());
-    for (int i = 0; ok && i < 4; i++) ok = put_str(names[i], strlen(names[i])) && put_str(hdrs[i], strlen(hdrs[i]));
+    for (int i = 0; ok && i < 5; i++) ok = put_str(names[i], strlen(names[i])) && put_str(hdrs[i], strlen(hdrs[i]));
     for (size_t i = 0; ok && i < flags.size(); i++) ok = put_str(flags[i].data(), flags[i].size());
     uint32_t resp[2] = {0, 0};
     uint64_t n = 0;
@@ -743,10 +781,10 @@ std::shared_ptr<const RtcCode> rtc_compile(const std::string& src, const std::st
         if (!out->code.empty()) rtc_disk_store(key, out->code);
         return out;
     }
-    const char* hdrs[] = {pt_rtc_src_trace, pt_rtc_src_math, pt_rtc_src_stack, pt_rtc_src_hip};
-    const char* names[] = {"pt_trace.h", "pt_math.h", "pt_raystack.h", "pt_hip.h"};
+    const char* hdrs[] = {pt_rtc_src_trace, pt_rtc_src_math, pt_rtc_src_stack, pt_rtc_src_lds, pt_rtc_src_hip};
+    const char* names[] = {"pt_trace.h", "pt_math.h", "pt_raystack.h", "pt_flatlds.h", "pt_hip.h"};
     hiprtcProgram prog;
-    if (hiprtcCreateProgram(&prog, src.c_str(), "pt_trace_flat_rtc.hip", 4, hdrs, names) != HIPRTC_SUCCESS) {
+    if (hiprtcCreateProgram(&prog, src.c_str(), "pt_trace_flat_rtc.hip", 5, hdrs, names) != HIPRTC_SUCCESS) {
         out->status = "hiprtcCreateProgram failed";
         return out;
     }
@@ -886,7 +924,8 @@ int pt_rtc_check(const pt_scene* scene, char* src_out, size_t cap) {
         return set_error(PT_E_ARG, "scene has no flat leaf list (%d leaves, %d triangles)", ps.num_leaves, ps.num_tris);
     const std::string src =
         rtc_flat_source(ps.leaves, ps.num_leaves, scene_has_specular(ps), ps.coords_small, albedo_x2_ok(ps), scene_dark(ps),
-                        scene_emit_box(ps, scene_dark(ps)));
+                        scene_emit_box(ps, scene_dark(ps)),
+                        rtc_baked(ps.num_tris, scene_has_specular(ps), flat_box_pairs(ps.leaves, ps.num_leaves)));
     if (src_out && cap) {
         const size_t n = std::min(cap - 1, src.size());
         memcpy(src_out, src.data(), n);
@@ -908,7 +947,8 @@ int pt_debug_rtc_start(const pt_scene* scene) {
         return set_error(PT_E_ARG, "scene has no flat leaf list (%d leaves, %d triangles)", ps.num_leaves, ps.num_tris);
     const RtcFuture f = rtc_job(
         rtc_flat_source(ps.leaves, ps.num_leaves, scene_has_specular(ps), ps.coords_small, albedo_x2_ok(ps), scene_dark(ps),
-                        scene_emit_box(ps, scene_dark(ps))));
+                        scene_emit_box(ps, scene_dark(ps)),
+                        rtc_baked(ps.num_tris, scene_has_specular(ps), flat_box_pairs(ps.leaves, ps.num_leaves))));
     return f.wait_for(std::chrono::seconds(0)) == std::future_status::ready ? 0 : 1;
 }
 

@@ -20,6 +20,7 @@
 
 #include "pt_hip.h"
 #include "pt_math.h"
+#include "pt_flatlds.h"
 #include "pt_raystack.h"
 
 namespace pt {
@@ -306,6 +307,134 @@ __device__ __forceinline__ const __attribute__((address_space(4))) TraceArgs* ke
     return K;
 }
 
+// ---- The scene's and the launch's constants as the shared bodies read them.
+// One accessor layer, so that there is one body: ArgConsts for the kernels that do not know the
+// scene, BakedConsts (below) for the hipRTC scene kernel, chosen by BoxMask::kBaked (KConsts).
+// ArgConsts reads every value from the kernel arguments where it is used — A.x wherever the
+// compiler keeps or reloads it, the others re-read from the kernarg segment (a scalar load and
+// a wait at the use) instead of being held in an SGPR that the loop's register budget spills.
+struct ArgConsts {
+    static constexpr bool kBaked = false;
+    static constexpr bool kThetaTab = true;  // the theta table's per-wave test is compiled in
+    ArgConsts() = default;
+    __device__ __forceinline__ explicit ArgConsts(const TraceArgs&) {}
+    __device__ __forceinline__ int num_tri4(const TraceArgs& A) const { return A.num_tri4; }
+    __device__ __forceinline__ int num_mat4(const TraceArgs& A) const { return A.num_mat4; }
+    __device__ __forceinline__ int depth(const TraceArgs& A) const { return A.depth; }
+    __device__ __forceinline__ int pair_queue(const TraceArgs& A) const { return A.pair_queue; }
+    __device__ __forceinline__ bool pairs_on(const TraceArgs& A) const { return A.pair_queue > 0; }
+    __device__ __forceinline__ bool fold_unrolled() const { return kernarg_args()->rec_size <= 4; }
+    __device__ __forceinline__ int theta_lanes() const { return kernarg_args()->theta_lanes; }
+    __device__ __forceinline__ uint32_t* flags() const { return kernarg_args()->flags; }
+    __device__ __forceinline__ bool flags_pm() const { return kernarg_args()->flags_pm != 0; }
+    __device__ __forceinline__ float* radiance(const TraceArgs& A) const { return A.radiance; }
+    // what only the rare paths read (the exact walk, a queue overflow)
+    __device__ __forceinline__ const float4* nodes(const TraceArgs& A) const { return A.nodes; }
+    __device__ __forceinline__ const float4* leaves(const TraceArgs& A) const { return A.leaves; }
+    __device__ __forceinline__ int* exact_stack(const TraceArgs& A) const {
+        return A.exact_stack + (size_t)blockIdx.x * A.exact_rows * kBlock;
+    }
+    // the flat block's LDS arrays (pt_flatlds.h); box_bytes: the mask's box table (0 in the offline
+    // kernels; a scene kernel built with PT_KCONST=0 and box-level pairs has one)
+    __device__ __forceinline__ FlatLds lds(const TraceArgs& A, unsigned box_bytes) const {
+        return flat_lds_layout((unsigned)A.num_tri4, (unsigned)A.num_mat4, box_bytes, (unsigned)A.pair_queue,
+                               (unsigned)A.rec_size);
+    }
+    // the record bases formed from the kernarg segment where they are used
+    __device__ __forceinline__ unsigned rec_tri_at(unsigned box_bytes) const {
+        const auto* K = kernarg_args();
+        return flat_lds_fixed((unsigned)K->num_tri4, (unsigned)K->num_mat4, box_bytes) +
+               2u * kFlatLdsWaves * (unsigned)K->pair_queue;
+    }
+    __device__ __forceinline__ unsigned rec_cos_at(unsigned rec_tri) const {
+        return rec_tri + 2u * kFlatLdsBlock * (unsigned)kernarg_args()->rec_size;
+    }
+};
+
+// The hipRTC scene kernel (PT_KCONST, on by default): what pt_ctx_set_scene fixes is a constant of
+// the generated source (M::kNumTri4, kNumMat4, kBoxTabBytes, kPairs, kThetaLanes: the code that a
+// value rules out is not compiled), and what a launch fixes (depth, rec_size, pair_queue and the
+// two LDS bases after them) is read once, before the loop, into scalar registers the constants
+// free. Pinned through an empty asm: a value the compiler can see as a kernarg load it loads
+// again at every use (machine LICM is off for these kernels), with a wait each time.
+// PT_KPIN: which launch values are pinned, 1 depth | 2 pair_queue | 4 the record bases; the others
+// are loaded where they are used, as ArgConsts does (A/B hook through PT_RTC_DEFINES). All three are
+// on in every scene kernel: with the specular sampler they cost spilled SGPRs (19 against 12) and
+// still measured faster than any smaller mask.
+#ifndef PT_KPIN
+#define PT_KPIN 7
+#endif
+template <typename M>
+struct BakedConsts {
+    static constexpr bool kBaked = true;
+    static constexpr bool kThetaTab = M::kThetaLanes > 0;
+    int depth_, pair_queue_;
+    unsigned rec_tri_, rec_cos_;
+    __device__ __forceinline__ static int pin(int v) {
+        asm volatile("" : "+s"(v));
+        return v;
+    }
+    __device__ __forceinline__ explicit BakedConsts(const TraceArgs& A) {
+        depth_ = (PT_KPIN & 1) ? pin(A.depth) : 0;
+        pair_queue_ = (PT_KPIN & 2) ? pin(A.pair_queue) : 0;
+        const FlatLds l = lds(A, (unsigned)M::kBoxTabBytes);
+        rec_tri_ = (PT_KPIN & 4) ? (unsigned)pin((int)l.rec_tri) : 0u;
+        rec_cos_ = (PT_KPIN & 4) ? (unsigned)pin((int)l.rec_cos) : 0u;
+    }
+    __device__ __forceinline__ int num_tri4(const TraceArgs&) const { return M::kNumTri4; }
+    __device__ __forceinline__ int num_mat4(const TraceArgs&) const { return M::kNumMat4; }
+    __device__ __forceinline__ int depth(const TraceArgs&) const { return (PT_KPIN & 1) ? depth_ : kernarg_args()->depth; }
+    __device__ __forceinline__ int pair_queue(const TraceArgs&) const {
+        return (PT_KPIN & 2) ? pair_queue_ : kernarg_args()->pair_queue;
+    }
+    __device__ __forceinline__ bool pairs_on(const TraceArgs&) const { return M::kPairs; }
+    // the unwinding, the exact walk and a queue overflow are rare: what only they read is loaded
+    // there, and holds no register across the loop
+    __device__ __forceinline__ bool fold_unrolled() const { return kernarg_args()->rec_size <= 4; }
+    __device__ __forceinline__ const float4* nodes(const TraceArgs&) const { return kernarg_args()->nodes; }
+    __device__ __forceinline__ const float4* leaves(const TraceArgs&) const { return kernarg_args()->leaves; }
+    __device__ __forceinline__ int* exact_stack(const TraceArgs&) const {
+        const auto* K = kernarg_args();
+        return K->exact_stack + (size_t)blockIdx.x * K->exact_rows * kBlock;
+    }
+    __device__ __forceinline__ int theta_lanes() const { return M::kThetaLanes; }
+    // The slab and its flag bits, read where a path ends: pinned before the loop they cost three
+    // more spilled SGPRs, and the camera position became a load at every path start (§3.27).
+    __device__ __forceinline__ uint32_t* flags() const { return kernarg_args()->flags; }
+    __device__ __forceinline__ bool flags_pm() const { return kernarg_args()->flags_pm != 0; }
+    __device__ __forceinline__ float* radiance(const TraceArgs& A) const { return A.radiance; }
+    __device__ __forceinline__ FlatLds lds(const TraceArgs& A, unsigned) const {
+        return flat_lds_layout((unsigned)M::kNumTri4, (unsigned)M::kNumMat4, (unsigned)M::kBoxTabBytes, (unsigned)A.pair_queue,
+                               (unsigned)A.rec_size);
+    }
+    __device__ __forceinline__ unsigned rec_tri_at(unsigned) const {
+        if (PT_KPIN & 4) return rec_tri_;
+        return flat_lds_fixed((unsigned)M::kNumTri4, (unsigned)M::kNumMat4, (unsigned)M::kBoxTabBytes) +
+               2u * kFlatLdsWaves * (unsigned)kernarg_args()->pair_queue;
+    }
+    __device__ __forceinline__ unsigned rec_cos_at(unsigned rec_tri) const {
+        return (PT_KPIN & 4) ? rec_cos_ : rec_tri + 2u * kFlatLdsBlock * (unsigned)kernarg_args()->rec_size;
+    }
+};
+
+// BoxMask::kBaked (the generated SceneBoxMask alone has it) picks the layer.
+template <typename M, typename = void>
+struct KConsts {
+    using type = ArgConsts;
+};
+template <typename M>
+struct KConsts<M, decltype((void)M::kBaked)> {
+    template <bool kOn, typename T, typename F>
+    struct Pick {
+        using type = T;
+    };
+    template <typename T, typename F>
+    struct Pick<false, T, F> {
+        using type = F;
+    };
+    using type = typename Pick<M::kBaked, BakedConsts<M>, ArgConsts>::type;
+};
+
 // The last-ray rule of shade, by where the emitter box E comes from.
 // NoEmitReject: not compiled in (caller-supplied rays and gradients, pt_paths.hip, pt_grad.hip).
 struct NoEmitReject {
@@ -591,17 +720,18 @@ __device__ __forceinline__ float lane_float(int addr, float v) {
 // equal t resolves to the lower rank — exactly the reference's winner, in any order.
 // Must be called by all 64 lanes (wave-uniform control flow); `mask` = the lane's
 // passing leaves (0 for a lane without a ray). The queue is the wave's own LDS array of
-// A.pair_queue 16-bit entries (lane << 6 | leaf), written linearly; when the wave's pairs
+// pair_queue 16-bit entries (lane << 6 | leaf), written linearly; when the wave's pairs
 // exceed it, the lanes test their own leaves in a loop (flat_tri_loop, same result).
-template <typename BoxMask, typename TriPtr, typename LeafPtr>
+template <typename BoxMask, typename TriPtr, typename LeafPtr, typename KC = ArgConsts>
 __device__ __forceinline__ int intersect_flat_pairs(const TraceArgs& A, unsigned long long mask, LeafPtr lleaves,
                                                     TriPtr tris, uint16_t* __restrict__ queue,
                                                     unsigned long long* __restrict__ best, int tid, int lane, v3 o,
-                                                    v3 d, float& t_out, const uint16_t* __restrict__ boxtab) {
+                                                    v3 d, float& t_out, const uint16_t* __restrict__ boxtab,
+                                                    const KC& kc = KC()) {
     const uint32_t c = (uint32_t)__popcll(mask);
     const uint32_t incl = wave_incl_scan(c);
     const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-    if (total > (uint32_t)A.pair_queue) {
+    if (total > (uint32_t)kc.pair_queue(A)) {
         if constexpr (BoxMask::kBoxPairs) return flat_box_loop(mask, boxtab, tris, o, d, t_out);
         return flat_tri_loop(mask, lleaves, tris, o, d, t_out);
     }
@@ -1782,11 +1912,13 @@ constexpr int kShadeGo = 0, kShadeEnd = 1, kShadeEndEarly = 2;
 // A policy with the slab member (RejSlab: the flat body) also gets inv = 1 / d of the new ray in
 // `inv`, computed here for the lanes whose path goes on and used by the slab test; the other
 // policies leave `inv` alone and compile what they compiled without it.
-template <bool kSpecular = true, typename RecT = int, bool kIds = false, typename Rej = NoEmitReject>
+// KC: where the depth and the theta table's lane bound come from (ArgConsts / BakedConsts).
+template <bool kSpecular = true, typename RecT = int, bool kIds = false, typename Rej = NoEmitReject,
+          typename KC = ArgConsts>
 __device__ __forceinline__ int shade_inv(const TraceArgs& A, const float4* __restrict__ mats,
                                           const float4* __restrict__ tris, RecT* __restrict__ rec_tri,
                                           float* __restrict__ rec_cos, int tid, int hit, float t, Lcg& g, v3& o,
-                                          v3& d, v3& inv, int& k, v3& L) {
+                                          v3& d, v3& inv, int& k, v3& L, const KC& kc = KC()) {
     L = v3{0.0f, 0.0f, 0.0f};
     if (hit < 0) return kShadeEnd;  // miss -> 0 (also depth <= 0)
 #ifdef PT_EXP_DUP_SHADE  // measurement only: the hit record and material reads, face-forward and hit point once more
@@ -1814,7 +1946,7 @@ __device__ __forceinline__ int shade_inv(const TraceArgs& A, const float4* __res
         L = v3{m1.x, m1.y, m1.z};
         return kShadeEnd;
     }
-    const int depth = A.depth;
+    const int depth = kc.depth(A);
     if (k + 1 >= depth) {
         // Last segment: trace(depth-1 == 0) returns 0, so the result is
         // emission + ((2*0)*albedo)*cos; the BRDF draw only advanced the
@@ -1852,7 +1984,8 @@ __device__ __forceinline__ int shade_inv(const TraceArgs& A, const float4* __res
 #elif PT_THETA_TAB == 2
         // by wave: few lanes sampling -> the table (little memory traffic, the computed form
         // would run at low lane utilisation); many -> computed (no table traffic)
-        if ((int)__popcll(__ballot(true)) <= kernarg_args()->theta_lanes)
+        // (KC::kThetaTab false: a scene kernel whose scene never uses the table holds neither)
+        if (KC::kThetaTab && (int)__popcll(__ballot(true)) <= kc.theta_lanes())
             nd = hemisphere_dir_tab(g, n, kernarg_args()->theta_tab);
         else
             nd = hemisphere_dir(g, n);
@@ -1942,10 +2075,10 @@ __device__ __forceinline__ uint32_t slab_index(const TraceArgs& A, int s, int q)
 #ifndef PT_DARK_SKIP
 #define PT_DARK_SKIP 1
 #endif
-template <typename RecT, bool kAlbedoX2 = false, bool kDarkKnown = false, bool kDark = false>
+template <typename RecT, bool kAlbedoX2 = false, bool kDarkKnown = false, bool kDark = false, typename KC = ArgConsts>
 __device__ __forceinline__ void finish_path(const TraceArgs& A, const float4* __restrict__ mats,
                                             const RecT* __restrict__ rec_tri, const float* __restrict__ rec_cos,
-                                            int tid, int k, v3 L, uint32_t at) {
+                                            int tid, int k, v3 L, uint32_t at, const KC& kc = KC()) {
 #ifdef PT_EXP_NO_FOLD  // timing experiment only (wrong images): skip the unwinding
     k = 0;
 #endif
@@ -1956,7 +2089,7 @@ __device__ __forceinline__ void finish_path(const TraceArgs& A, const float4* __
 #ifndef PT_FOLD_UNROLL
 #define PT_FOLD_UNROLL 1
 #endif
-    if (PT_FOLD_UNROLL && kernarg_args()->rec_size <= 4) {  // uniform; re-read, not held in a spilled SGPR
+    if (PT_FOLD_UNROLL && kc.fold_unrolled()) {  // rec_size <= 4, uniform (ArgConsts: re-read, not held in a spilled SGPR)
         // depth <= 5: every record of the path is loaded up front (predicated on j < k),
         // so the unwinding waits for two LDS round trips instead of two per level
         int tj[4];
@@ -2018,11 +2151,11 @@ __device__ __forceinline__ void finish_path(const TraceArgs& A, const float4* __
     if (L.x == 12345.0f)
 #endif
     // a flagged slab takes only the records of paths that do not end dark (TraceArgs::flags)
-    uint32_t* fl = kernarg_args()->flags;
+    uint32_t* fl = kc.flags();
     if (unwind || !fl)
-        *reinterpret_cast<float3*>(A.radiance + 3 * (size_t)at) = make_float3(L.x, L.y, L.z);  // slab_at's layout
+        *reinterpret_cast<float3*>(kc.radiance(A) + 3 * (size_t)at) = make_float3(L.x, L.y, L.z);  // slab_at's layout
     if (unwind && fl) {  // rare (paths that end on an emitter): at = sample * npix + pixel
-        if (kernarg_args()->flags_pm) {
+        if (kc.flags_pm()) {
             const uint32_t sm = fdiv(at, A.div_npix), q = at - sm * (uint32_t)A.npix;
             atomicOr(fl + flag_word(sm, q, (uint32_t)A.npix), 1u << (sm & 31u));
         } else {
@@ -2056,9 +2189,10 @@ __device__ __forceinline__ void count_early_wave(const TraceArgs& A, int lane, u
 // The megakernel body of the flat path (scenes with <= 64 leaves).
 // BoxMask: the leaf-box test (the kernel-argument table, or the hipRTC-generated one with
 // the scene's planes as constants). One loop iteration = one path segment of every lane.
-// LDS (small, so that many blocks fit): [triangles: num_tri4 float4] [materials:
-// num_mat4 float4] [pair queues: pair_queue x uint16 per wave] [records: rec_size x
-// kBlock x (uint16 triangle, float cos)] [best: kBlock x u64]. The node array and the
+// LDS (small, so that many blocks fit): the layout of pt_flatlds.h — triangles, materials,
+// prefetched camera rays, winners (best), box table, then the launch-sized pair queues
+// (pair_queue x uint16 per wave) and records (rec_size x kBlock x (uint16 triangle, float cos)).
+// The node array and the
 // leaf list are read from global memory (L1/L2): only the rare exact walk (a zero
 // direction component) and queue overflows touch them; the exact walk's stack is in HBM.
 // threadIdx.x re-read at a use: the per-lane LDS addresses formed from it (best[tid], the
@@ -2097,36 +2231,40 @@ __device__ __forceinline__ int fresh_tid() {
 }
 
 // The flat kernel's path-record bases, formed from the kernarg segment where they are used
-// (scalar loads and adds) instead of being held in SGPRs across the loop (spilled to VGPR
-// lanes at the hipRTC kernel's register budget).
+// (scalar loads and adds) instead of being held in SGPRs across the loop (ArgConsts); the
+// hipRTC scene kernel holds them in the SGPRs its constants free (BakedConsts).
 struct FlatRecs {
     uint16_t* tri;
     float* cos;
 };
-__device__ __forceinline__ FlatRecs flat_records(float4* lds4) {
-    const auto* K = kernarg_args();
-    uint16_t* rt = reinterpret_cast<uint16_t*>(lds4 + K->num_tri4 + K->num_mat4) + (kBlock / kWave) * K->pair_queue;
-    return FlatRecs{rt, reinterpret_cast<float*>(rt + K->rec_size * kBlock)};
+template <typename BoxMask, typename KC>
+__device__ __forceinline__ FlatRecs flat_records(float4* lds4, const KC& kc) {
+    char* lds = reinterpret_cast<char*>(lds4);
+    const unsigned rt = kc.rec_tri_at(flat_box_tab_bytes((unsigned)BoxMask::kBoxes));
+    return FlatRecs{reinterpret_cast<uint16_t*>(lds + rt), reinterpret_cast<float*>(lds + kc.rec_cos_at(rt))};
 }
+static_assert(kFlatLdsBlock == (unsigned)kBlock && kFlatLdsWaves == (unsigned)(kBlock / kWave), "pt_flatlds.h");
 
 template <typename BoxMask>
 __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
     extern __shared__ float4 lds4[];
     const int tid = threadIdx.x;
     const int lane = tid & (kWave - 1);
-    float4* s_tris = lds4;
-    float4* s_mats = s_tris + A.num_tri4;
-    uint16_t* queues = reinterpret_cast<uint16_t*>(s_mats + A.num_mat4);
-    uint16_t* rec_tri = queues + (kBlock / kWave) * A.pair_queue;
-    float* rec_cos = reinterpret_cast<float*>(rec_tri + A.rec_size * kBlock);
-    unsigned long long* best = reinterpret_cast<unsigned long long*>(rec_cos + A.rec_size * kBlock);
-    float4* next_ray = reinterpret_cast<float4*>(best + kBlock);  // prefetched camera ray: d.xyz, LCG state
-    uint32_t* next_at = reinterpret_cast<uint32_t*>(next_ray + kBlock);  // its item = slab offset
-    uint16_t* boxtab = reinterpret_cast<uint16_t*>(next_at + kBlock);     // box-level pairs: box -> its triangles
+    using KC = typename KConsts<BoxMask>::type;
+    const KC kc(A);
+    const FlatLds lay = kc.lds(A, flat_box_tab_bytes((unsigned)BoxMask::kBoxes));  // pt_flatlds.h: the scene-fixed arrays first, the launch's queues and records last
+    char* lds = reinterpret_cast<char*>(lds4);
+    float4* s_tris = reinterpret_cast<float4*>(lds + lay.tris);
+    float4* s_mats = reinterpret_cast<float4*>(lds + lay.mats);
+    float4* next_ray = reinterpret_cast<float4*>(lds + lay.next_ray);  // prefetched camera ray: d.xyz, LCG state
+    unsigned long long* best = reinterpret_cast<unsigned long long*>(lds + lay.best);
+    uint32_t* next_at = reinterpret_cast<uint32_t*>(lds + lay.next_at);  // its item = slab offset
+    uint16_t* boxtab = reinterpret_cast<uint16_t*>(lds + lay.boxtab);    // box-level pairs: box -> its triangles
+    uint16_t* queues = reinterpret_cast<uint16_t*>(lds + lay.queues);
     if constexpr (BoxMask::kBoxPairs)
         for (int i = tid; i < BoxMask::kBoxes; i += kBlock) boxtab[i] = BoxMask::kBoxTab[i];
-    for (int i = tid; i < A.num_tri4; i += kBlock) s_tris[i] = A.tris[i];
-    for (int i = tid; i < A.num_mat4; i += kBlock) {
+    for (int i = tid; i < kc.num_tri4(A); i += kBlock) s_tris[i] = A.tris[i];
+    for (int i = tid; i < kc.num_mat4(A); i += kBlock) {
         float4 m = A.mats[i];
         if (BoxMask::kAlbedoX2 && !(i & 1)) m = make_float4(m.x, 2.0f * m.y, 2.0f * m.z, 2.0f * m.w);  // row's albedo
         s_mats[i] = m;
@@ -2134,8 +2272,7 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
     __syncthreads();
     const float4* __restrict__ mats = s_mats;
     const float4* __restrict__ tris = s_tris;
-    uint16_t* wq = queues + __builtin_amdgcn_readfirstlane(tid >> 6) * A.pair_queue;
-    int* xstk = A.exact_stack + (size_t)blockIdx.x * A.exact_rows * kBlock;
+    uint16_t* wq = queues + __builtin_amdgcn_readfirstlane(tid >> 6) * kc.pair_queue(A);
 
     bool alive = true;      // the lane's generator may still produce paths
     bool active = false;    // lane has a path in flight (slab offset `at`)
@@ -2278,8 +2415,8 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
         // intersecting (render.h:37)
         float t = 0.0f;
         int hit = -1;
-        const bool tr = active && A.depth > 0;
-        if (A.depth > 0) n_rays += (unsigned long long)__popcll(__ballot(tr));
+        const bool tr = active && kc.depth(A) > 0;
+        if (kc.depth(A) > 0) n_rays += (unsigned long long)__popcll(__ballot(tr));
         // bvh.h:157 inv = 1 / d. Waves whose lanes all have finite inv take the IEEE
         // min/max slab test (identical result, see slab_hit_finite).
         if constexpr (!kCarry) inv = rcp3_exact(d, tr);
@@ -2288,7 +2425,7 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
         // finite: |1 / d| <= 2^60 and |o| < 2^60 (scene coordinates < 2^60: the host's
         // condition), so |t| < 2^122; others take the exact walk as zero components do
         const bool fast = !forced && __all(!tr || (BoxMask::kSignMask ? bounded_ray(o, inv) : all_finite(inv)));
-        if (fast && A.pair_queue > 0) {
+        if (fast && kc.pairs_on(A)) {
             // wave-uniform branch: all 64 lanes take part in the pair queue
             if (PT_PRIO_MASK) __builtin_amdgcn_s_setprio(PT_PRIO_MASK);
             unsigned long long mask = BoxMask::mask(A, o, inv);
@@ -2321,14 +2458,15 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
             t = 1.0f;
 #else
             if (PT_PRIO_PAIRS) __builtin_amdgcn_s_setprio(PT_PRIO_PAIRS);
-            hit = intersect_flat_pairs<BoxMask>(A, mask, A.leaves, tris, wq, best, fresh_tid(), lane, o, d, t, boxtab);
+            hit = intersect_flat_pairs<BoxMask>(A, mask, kc.leaves(A), tris, wq, best, fresh_tid(), lane, o, d, t, boxtab, kc);
             if (PT_PRIO_PAIRS) __builtin_amdgcn_s_setprio(0);
 #endif
             PT_STAMP(st_b3)
             PT_STAMP_ADD(2, st_b2, st_b3)
         } else if (tr) {
-            if (fast) hit = intersect_flat<BoxMask>(A, A.leaves, tris, o, d, inv, t, boxtab);
-            else hit = intersect_tree<false>(A.nodes, tris, xstk, tid, o, d, inv, t);
+            // (fast here: the pair queues are off; a scene kernel that has them on compiles no per-lane loop)
+            if (fast && !kc.pairs_on(A)) hit = intersect_flat<BoxMask>(A, kc.leaves(A), tris, o, d, inv, t, boxtab);
+            else hit = intersect_tree<false>(kc.nodes(A), tris, kc.exact_stack(A), tid, o, d, inv, t);
         }
         PT_STAMP(st_c)
 
@@ -2336,9 +2474,9 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
         v3 L{0.0f, 0.0f, 0.0f};
         if (PT_PRIO_SHADE) __builtin_amdgcn_s_setprio(PT_PRIO_SHADE);
         if (active) {
-            const FlatRecs R = flat_records(lds4);
+            const FlatRecs R = flat_records<BoxMask>(lds4, kc);
             sh = shade_inv<BoxMask::kSpecular, uint16_t, false, typename BoxMask::EmitRej>(
-                A, mats, tris, R.tri, R.cos, fresh_tid(), hit, t, g, o, d, inv, k, L);
+                A, mats, tris, R.tri, R.cos, fresh_tid(), hit, t, g, o, d, inv, k, L, kc);
         }
         if (PT_PRIO_SHADE) __builtin_amdgcn_s_setprio(0);
         const bool end = sh != kShadeGo;
@@ -2351,9 +2489,9 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
         PT_STAMP(st_d)
         if (end) {
             if (PT_PRIO_FOLD) __builtin_amdgcn_s_setprio(PT_PRIO_FOLD);
-            const FlatRecs R = flat_records(lds4);
+            const FlatRecs R = flat_records<BoxMask>(lds4, kc);
             finish_path<uint16_t, BoxMask::kAlbedoX2, BoxMask::kDarkKnown, BoxMask::kDark>(A, mats, R.tri, R.cos,
-                                                                                        fresh_tid(), k, L, at);
+                                                                                        fresh_tid(), k, L, at, kc);
             if (PT_PRIO_FOLD) __builtin_amdgcn_s_setprio(0);
             active = false;
         }
