@@ -105,6 +105,21 @@ int pt_debug_emit_reject(const float* box6, const float* org, const float* dir, 
  * n rays: box6 and org as above, inv 3 floats each (the kernels pass 1 / dir) -> out[i] = 1 if E
  * itself fails the slab test, under the predicate's guard, or E is empty (lb > rt on an axis). */
 int pt_debug_emit_slab_reject(const float* box6, const float* org, const float* inv, int64_t n, uint8_t* out);
+/* Test hook for the one-verdict-per-ray policy (PT_DOMAIN_ONCE; rcp3_exact_v and
+ * emit_slab_reject_given, pt_math.h) on n rays against ONE box: box6 = {E lb.xyz, E rt.xyz}, org / dir
+ * 3 floats each; unit != 0 runs the unit-vector form of the predicate (the bounce's), 0 the two-sided
+ * one (camera rays, the specular sample). device < 0: the host form, each ray its own wave; device
+ * >= 0: one block of 256 threads on that device, ray i in lane i mod 64 of wave (i / 64) mod 4, where
+ * the verdict is the wave's. out[6i..] = {rcp3_exact's own range predicate holds, finite_nonzero of
+ * every component of inv (the slab guard's inv half), all_finite(inv) (the top-of-iteration test),
+ * the new verdict (1 = "in the domain", the wave did not fall back), emit_slab_reject, the guard-free
+ * form as shade_inv calls it (inv half: the verdict, or the per-lane test in a wave that fell back)};
+ * inv3[3i..] = rcp3_exact_v's result. */
+int pt_debug_domain_once(int device, const float* box6, const float* org, const float* dir, int64_t n, int unit,
+                         uint8_t* out, float* inv3);
+/* Test hook, no device needed: hemisphere_dir (pt_math.h, the host form) from LCG state lcg[i] about
+ * the normal nrm[3i..] -> dir3[3i..]. */
+int pt_debug_hemisphere_dir(const uint32_t* lcg, const float* nrm, int64_t n, float* dir3);
 /* Test hook, no device needed: the emitter box the host computes for `scene` (the union of the
  * tree's leaf boxes that hold an EMIT triangle; lb = +inf, rt = -inf when there is none, which
  * rejects every last ray). Returns 1 if the rule is on (a dark scene, PT_EMIT_REJECT not 0), 0 if

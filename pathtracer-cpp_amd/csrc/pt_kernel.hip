@@ -268,6 +268,46 @@ __global__ void pt_math_kernel(int which, const float* __restrict__ in, float* _
     }
 }
 
+// pt_debug_domain_once (test hook): the three predicates the flat body asked of a ray, the one
+// verdict it asks with PT_DOMAIN_ONCE, and the slab rule with and without the inv half of its
+// guard, as shade_inv calls them. One function for the host and the device form.
+template <bool kUnit>
+PT_HD void domain_once_probe(v3 elb, v3 ert, v3 o, v3 d, uint8_t* r, float* inv3) {
+    const float ax = __builtin_fabsf(d.x), ay = __builtin_fabsf(d.y), az = __builtin_fabsf(d.z);
+    bool in = __builtin_fminf(__builtin_fminf(ax, ay), az) >= 0x1p-126f;  // rcp3_exact's predicate
+    if (!kUnit) in = in && __builtin_fmaxf(__builtin_fmaxf(ax, ay), az) <= 0x1p126f;
+    bool fell;
+    const v3 inv = rcp3_exact_v<kUnit>(d, fell);
+    const bool inv_ok = fell ? finite_nonzero3(inv) : true;
+    r[0] = in;
+    r[1] = finite_nonzero3(inv);
+    r[2] = all_finite(inv);
+    r[3] = !fell;
+    r[4] = emit_slab_reject(elb, ert, o, inv);
+    r[5] = emit_slab_reject_given(elb, ert, o, inv, inv_ok);
+    inv3[0] = inv.x;
+    inv3[1] = inv.y;
+    inv3[2] = inv.z;
+}
+// One block; every lane of a wave runs the same number of rounds (a lane past the end repeats the
+// last ray and stores nothing), so the wave's vote inside rcp3_exact_v sees whole waves.
+__global__ void pt_domain_once_kernel(const float* box6, const float* org, const float* dir, int n, int unit,
+                                      uint8_t* out, float* inv3) {
+    const v3 elb{box6[0], box6[1], box6[2]}, ert{box6[3], box6[4], box6[5]};
+    for (int base = 0; base < n; base += (int)blockDim.x) {
+        const int i = base + (int)threadIdx.x, j = i < n ? i : n - 1;
+        const v3 o{org[3 * j], org[3 * j + 1], org[3 * j + 2]}, d{dir[3 * j], dir[3 * j + 1], dir[3 * j + 2]};
+        uint8_t r[6];
+        float v[3];
+        if (unit) domain_once_probe<true>(elb, ert, o, d, r, v);
+        else domain_once_probe<false>(elb, ert, o, d, r, v);
+        if (i < n) {
+            for (int c = 0; c < 6; c++) out[6 * i + c] = r[c];
+            for (int c = 0; c < 3; c++) inv3[3 * i + c] = v[c];
+        }
+    }
+}
+
 // Exhaustive sweep of a fast exact sequence against the IEEE operation (test hook).
 __global__ void pt_sweep_kernel(int which, uint32_t lo, unsigned long long n, unsigned long long* bad,
                                 uint32_t* first) {
@@ -2894,6 +2934,59 @@ int pt_debug_emit_slab_reject(const float* box6, const float* org, const float* 
     for (int64_t i = 0; i < n; i++) {
         const float *b = box6 + 6 * i, *o = org + 3 * i, *v = inv + 3 * i;
         out[i] = emit_slab_reject(v3{b[0], b[1], b[2]}, v3{b[3], b[4], b[5]}, v3{o[0], o[1], o[2]}, v3{v[0], v[1], v[2]}) ? 1 : 0;
+    }
+    return PT_OK;
+}
+
+// Test hook: the one-verdict-per-ray policy's device functions (domain_once_probe) on n rays
+// against one box, on the host (device < 0) or in one block on a device.
+int pt_debug_domain_once(int device, const float* box6, const float* org, const float* dir, int64_t n, int unit,
+                         uint8_t* out, float* inv3) {
+    if (!box6 || !org || !dir || !out || !inv3 || n < 1 || n > (1 << 20))
+        return set_error(PT_E_ARG, "pt_debug_domain_once: bad argument");
+    if (device < 0) {
+        const v3 elb{box6[0], box6[1], box6[2]}, ert{box6[3], box6[4], box6[5]};
+        for (int64_t i = 0; i < n; i++) {
+            const v3 o{org[3 * i], org[3 * i + 1], org[3 * i + 2]}, d{dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]};
+            if (unit) domain_once_probe<true>(elb, ert, o, d, out + 6 * i, inv3 + 3 * i);
+            else domain_once_probe<false>(elb, ert, o, d, out + 6 * i, inv3 + 3 * i);
+        }
+        return PT_OK;
+    }
+    HIP_TRY(hipSetDevice(device));
+    const size_t fb = (size_t)n * 3 * sizeof(float);
+    float* dbuf = nullptr;  // box6 | org | dir | inv3, then the flags
+    uint8_t* dout = nullptr;
+    HIP_TRY(hipMalloc((void**)&dbuf, 6 * sizeof(float) + 3 * fb));
+    if (hipMalloc((void**)&dout, (size_t)n * 6) != hipSuccess) {
+        (void)hipFree(dbuf);
+        return set_error(PT_E_HIP, "hipMalloc failed");
+    }
+    float *dorg = dbuf + 6, *ddir = dorg + 3 * n, *dinv = ddir + 3 * n;
+    hipError_t e = hipMemcpy(dbuf, box6, 6 * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dorg, org, fb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(ddir, dir, fb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(pt_domain_once_kernel, dim3(1), dim3(256), 0, 0, dbuf, dorg, ddir, (int)n, unit, dout, dinv);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out, dout, (size_t)n * 6, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(inv3, dinv, fb, hipMemcpyDeviceToHost);
+    (void)hipFree(dbuf);
+    (void)hipFree(dout);
+    if (e != hipSuccess) return set_error(PT_E_HIP, "pt_debug_domain_once: %s", hipGetErrorString(e));
+    return PT_OK;
+}
+
+// Test hook (no device needed): hemisphere_dir's host form.
+int pt_debug_hemisphere_dir(const uint32_t* lcg, const float* nrm, int64_t n, float* dir3) {
+    if (!lcg || !nrm || !dir3 || n < 0) return set_error(PT_E_ARG, "pt_debug_hemisphere_dir: bad argument");
+    for (int64_t i = 0; i < n; i++) {
+        Lcg g{lcg[i]};
+        const v3 r = hemisphere_dir(g, v3{nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]});
+        dir3[3 * i] = r.x;
+        dir3[3 * i + 1] = r.y;
+        dir3[3 * i + 2] = r.z;
     }
     return PT_OK;
 }

@@ -159,6 +159,43 @@ PT_HD v3 rcp3_exact(v3 d, bool live = true) {
 #endif
 }
 
+// rcp3_exact that also hands its range predicate to the caller (PT_DOMAIN_ONCE):
+// `fell` is whether the wave ran the fallback, i.e. some lane active here failed the predicate (on
+// the host, where a lane is its own wave: whether this d failed it). The result has rcp3_exact's
+// bits. What !fell proves about every lane active at the call, per component i:
+//     inv_i = RN(1 / d_i) is finite and non-zero, and not NaN.
+// Proof, kUnit (d is hemisphere_dir's sample, the caller's condition).
+//   * d has no NaN and |d_i| <= 1: its components are sin / cos values of finite angles (the angles
+//     come from the LCG alone, the normal only picks the sign) and products of two of them;
+//     |sin|, |cos| <= 1 as floats (correctly rounded, 1 is a float) and RN(a b) <= 1 for
+//     |a|, |b| <= 1 by the monotonicity of rounding.
+//   * Without a NaN v_min3_f32 is the true minimum, so min |d_i| >= 2^-126 puts every |d_i| in
+//     [2^-126, 1], 1 / |d_i| in [1, 2^126], and RN of it (2^126 and 1 are floats) in the same
+//     interval: finite, non-zero, normal.
+// Proof, !kUnit (a camera ray, the specular sample: any float may arrive).
+//   * The predicate here is s = (|d_x| + |d_y|) + |d_z| <= 2^126 beside the minimum: an addition
+//     hands a NaN operand on and v_min3 / v_max3 do not, so a NaN component, which passes
+//     rcp3_exact's own two-sided test beside two components in range, fails this one; so does an
+//     infinite one. With neither, |d_i| <= s by monotonicity (the other terms are >= 0), and the
+//     minimum is the true one: every |d_i| in [2^-126, 2^126], so RN(1 / |d_i|) too.
+//   * The sum is stricter than max |d_i| <= 2^126 (by less than two binades); a lane in between
+//     takes the IEEE divisions, which give the same bits (rcp_newton is exact on its range).
+template <bool kUnit>
+PT_HD v3 rcp3_exact_v(v3 d, bool& fell) {
+    const float ax = __builtin_fabsf(d.x), ay = __builtin_fabsf(d.y), az = __builtin_fabsf(d.z);
+    bool out = !(__builtin_fminf(__builtin_fminf(ax, ay), az) >= 0x1p-126f);
+    if (!kUnit) out = out || !((ax + ay) + az <= 0x1p126f);
+#if defined(__HIP_DEVICE_COMPILE__) && PT_WAVE_GUARD
+    v3 r{rcp_newton(d.x), rcp_newton(d.y), rcp_newton(d.z)};
+    fell = wave_any(out);
+    if (__builtin_expect(fell, 0)) r = v3{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
+    return r;
+#else
+    fell = out;
+    return v3{rcp_exact(d.x), rcp_exact(d.y), rcp_exact(d.z)};
+#endif
+}
+
 // vec3::normalize = *this / length(): three correctly rounded divisions.
 PT_HD v3 normalize(v3 a) {
     float len = sqrt_exact(dot(a, a));
@@ -340,15 +377,18 @@ PT_HD bool emit_reject(v3 elb, v3 ert, v3 o, v3 d) {
 // literals the compiler folds that axis' min and max away.
 // Bitwise & and | as in emit_reject: straight-line compares, no branches per lane.
 PT_HD bool finite_nonzero(float x) { return ((int)(__builtin_fabsf(x) < __builtin_inff()) & (int)(x != 0.0f)) != 0; }
+PT_HD bool finite_nonzero3(v3 a) {
+    return ((int)finite_nonzero(a.x) & (int)finite_nonzero(a.y) & (int)finite_nonzero(a.z)) != 0;
+}
 // behind_only: the `tmax < 0` term alone, E lies behind the ray on some axis. Under the guard
 // that is emit_reject's condition without its bound on |d|: max(t1, t2) < 0 on axis a means
 // both differences are non-zero with the sign opposite to inv.a's, i.e. o.a < elb.a with
 // d.a < 0 or o.a > ert.a with d.a > 0, and emit_reject's proof gives the converse for |d.a| < 2.
 // The table kernels' sign-only hook runs this (a select on a flag, no second predicate in the
 // kernel); the hipRTC scene kernel's runs emit_reject itself.
-PT_HD bool emit_slab_reject_nonempty(v3 elb, v3 ert, v3 o, v3 inv, bool behind_only = false) {
-    const int guard = (int)finite_nonzero(inv.x) & (int)finite_nonzero(inv.y) & (int)finite_nonzero(inv.z) &
-                      (int)(__builtin_fabsf(o.x) < __builtin_inff()) & (int)(__builtin_fabsf(o.y) < __builtin_inff()) &
+// inv_ok: the inv half of the guard, made by the caller (emit_slab_reject_nonempty tests inv itself).
+PT_HD bool emit_slab_reject_core(v3 elb, v3 ert, v3 o, v3 inv, bool behind_only, bool inv_ok) {
+    const int guard = (int)inv_ok & (int)(__builtin_fabsf(o.x) < __builtin_inff()) & (int)(__builtin_fabsf(o.y) < __builtin_inff()) &
                       (int)(__builtin_fabsf(o.z) < __builtin_inff());
     const float t1x = (elb.x - o.x) * inv.x, t1y = (elb.y - o.y) * inv.y, t1z = (elb.z - o.z) * inv.z;
     const float t2x = (ert.x - o.x) * inv.x, t2y = (ert.y - o.y) * inv.y, t2z = (ert.z - o.z) * inv.z;
@@ -357,6 +397,9 @@ PT_HD bool emit_slab_reject_nonempty(v3 elb, v3 ert, v3 o, v3 inv, bool behind_o
     const float tmin = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(t1x, t2x), __builtin_fminf(t1y, t2y)),
                                        __builtin_fminf(t1z, t2z));
     return (guard & ((int)(tmax < 0.0f) | ((int)!behind_only & (int)(tmin > tmax)))) != 0;
+}
+PT_HD bool emit_slab_reject_nonempty(v3 elb, v3 ert, v3 o, v3 inv, bool behind_only = false) {
+    return emit_slab_reject_core(elb, ert, o, inv, behind_only, finite_nonzero3(inv));
 }
 // E empty (scene_emit_box's encoding of "no emitter leaf": elb = +inf, ert = -inf): there is no
 // box to hit, every last ray is rejected, whatever o and inv hold (the slab arithmetic on the
@@ -367,6 +410,17 @@ PT_HD bool emit_box_empty(v3 elb, v3 ert) {
 }
 PT_HD bool emit_slab_reject(v3 elb, v3 ert, v3 o, v3 inv) {
     return emit_box_empty(elb, ert) ? true : emit_slab_reject_nonempty(elb, ert, o, inv);
+}
+// emit_slab_reject_given (PT_DOMAIN_ONCE): the caller hands in the inv half of the guard, inv_ok.
+// A lane that holds rcp3_exact_v's verdict !fell passes `true`: every component of inv is finite
+// and non-zero (the proof is there), so no test of inv is issued; the lanes of a wave that fell
+// back pass finite_nonzero3(inv), which makes this the guarded form itself. The o half stays as it
+// is: o = (o' + d t) + 1e-4 n rounds three times and
+// can overflow for scene coordinates near the top of the float range, which no baked bound rules
+// out without a margin; and a form through v_max3_f32 would let a NaN component pass beside two
+// finite ones, so the three tests are already the short exact form.
+PT_HD bool emit_slab_reject_given(v3 elb, v3 ert, v3 o, v3 inv, bool inv_ok) {
+    return emit_box_empty(elb, ert) ? true : emit_slab_reject_core(elb, ert, o, inv, false, inv_ok);
 }
 
 // ------------------------------------------------------------------ Möller–Trumbore (triangle.h:25-44)

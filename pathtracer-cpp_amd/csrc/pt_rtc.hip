@@ -296,12 +296,18 @@ std::string flat_mask_source(const std::vector<f4>& leaves, int n, bool specular
               "        __device__ __forceinline__ static bool rejected_slab(v3 o, v3, v3 inv) {\n"
               "            return emit_slab_reject(v3{" + litf(emit.lo[0]) + ", " + litf(emit.lo[1]) + ", " + litf(emit.lo[2]) +
               "}, v3{" + litf(emit.hi[0]) + ", " + litf(emit.hi[1]) + ", " + litf(emit.hi[2]) + "}, o, inv);\n"
+              "        }\n"
+              // the same with the inv half of the guard handed in (PT_DOMAIN_ONCE, shade_inv)
+              "        __device__ __forceinline__ static bool rejected_slab_given(v3 o, v3, v3 inv, bool inv_ok) {\n"
+              "            return emit_slab_reject_given(v3{" + litf(emit.lo[0]) + ", " + litf(emit.lo[1]) + ", " + litf(emit.lo[2]) +
+              "}, v3{" + litf(emit.hi[0]) + ", " + litf(emit.hi[1]) + ", " + litf(emit.hi[2]) + "}, o, inv, inv_ok);\n"
               "        }\n    };\n";
     return std::string("#ifndef PT_FLAT_SIGN_MASK\n#define PT_FLAT_SIGN_MASK 0\n#endif\n#define KSIGN (PT_FLAT_SIGN_MASK && ") +
            (sign ? "1" : "0") + ")\n" + "#define KBOX " + (nbox > 0 ? "(!KSIGN)" : "0") + "\n" +
            "namespace pt {\nstruct SceneBoxMask {\n    static constexpr bool kSignMask = KSIGN;\n"
            "    static constexpr bool kBoxPairs = KBOX;\n    static constexpr bool kCamInvGen = PT_CAM_INV == 2;\n"
            "    static constexpr bool kRayStack = PT_RAY_STACK != 0;\n"
+           "    static constexpr bool kDomOnce = PT_DOMAIN_ONCE != 0;\n"  // DomOnce, pt_trace.h
            "    static constexpr int kBoxes = " + std::to_string(nbox) +
            ";\n    static constexpr uint16_t kBoxTab[" + std::to_string(std::max<size_t>(1, box_tab.size())) + "] = " + tabs +
            ";\n    static constexpr bool kMask32 = " +

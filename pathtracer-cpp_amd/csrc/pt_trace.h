@@ -486,6 +486,49 @@ struct RejSlab<Rej, decltype((void)Rej::kSlab)> {
     static constexpr bool value = Rej::kCompiled && Rej::kSlab;
 };
 
+// One domain verdict per ray, made where the ray is made (PT_DOMAIN_ONCE, default 1; DESIGN.md
+// §3.28; PT_RTC_DEFINES="PT_DOMAIN_ONCE=0" gives the code without it). The flat body asked three
+// times whether a ray's inv = 1 / d is finite: rcp3_exact's range predicate where the ray is made,
+// the inv half of emit_slab_reject's guard right after, and all_finite(inv) at the top of the next
+// iteration. The first implies the other two (rcp3_exact_v, pt_math.h), so with this policy
+//   * the verdict travels with the ray as bit 31 of its slab offset `at` (offsets are < 2^31, the
+//     host's check): kDomMark set = "not proven", clear = "inv finite, non-zero, not NaN". No
+//     register is added, scalar or vector: a wave whose rcp3_exact_v ran its fallback marks the
+//     lanes that made a ray there, in the fallback's own branch; the generator marks the stock's
+//     row (next_at) the same way, so the mark reaches whichever lane takes the ray;
+//   * the top of an iteration reads the marks of the lanes with a path (one compare); a wave with
+//     none is in the IEEE slab form's domain, all_finite(inv), without testing inv. A wave with a
+//     mark runs the per-lane test as before, takes the path that test picks, and clears the marks
+//     of the lanes that pass it;
+//   * shade_inv's slab rule runs without the inv half of its guard in a wave that did not fall back.
+// Compiled where the mask type asks for it (the generated SceneBoxMask: kDomOnce), the body
+// carries inv (RejSlab) and the mask needs no more than all_finite (the sign-bit mask's
+// bounded_ray also bounds |inv| by 2^60 and |o|, which rcp3_exact's predicate does not give: such
+// a kernel keeps its own test). Every other kernel compiles what it compiled.
+#ifndef PT_DOMAIN_ONCE
+#define PT_DOMAIN_ONCE 1
+#endif
+constexpr uint32_t kDomMark = 0x80000000u;
+// A lane's bool from a wave-uniform 64-bit lane mask with no vector instruction (the mask becomes
+// the branch's exec mask). The intrinsic by its own name: the runtime compiler does not declare
+// the builtin of the same meaning that the offline one has.
+// The argument must be wave-uniform (a ballot or scalar arithmetic on ballots): the result is
+// undefined otherwise. tests/test_domain_once_gpu.py renders through both forms' only user.
+#if defined(__has_builtin) && __has_builtin(__builtin_amdgcn_inverse_ballot_w64)
+__device__ __forceinline__ bool pt_lane_of_mask(unsigned long long m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+#else
+extern "C" __device__ bool pt_lane_of_mask(unsigned long long) __asm("llvm.amdgcn.inverse.ballot.i64");
+#endif
+template <typename M, typename = void>
+struct DomOnce {
+    static constexpr bool value = false, kMasks = false;
+};
+template <typename M>
+struct DomOnce<M, decltype((void)M::kDomOnce)> {
+    static constexpr bool value = M::kDomOnce && !M::kSignMask && RejSlab<typename M::EmitRej>::value;
+    static constexpr bool kMasks = M::kDomOnce;  // the lane-mask restatements ride on the same switch
+};
+
 struct NodeBox {
     v3 lb, rt;
     int a, b;
@@ -1913,12 +1956,16 @@ constexpr int kShadeGo = 0, kShadeEnd = 1, kShadeEndEarly = 2;
 // `inv`, computed here for the lanes whose path goes on and used by the slab test; the other
 // policies leave `inv` alone and compile what they compiled without it.
 // KC: where the depth and the theta table's lane bound come from (ArgConsts / BakedConsts).
+// kDom (DomOnce: the flat body alone): *dom_at is the lane's slab offset, whose bit kDomMark is set
+// here when the wave's rcp3_exact_v fell back; a wave that did not runs the slab rule without the
+// inv half of its guard (Rej::rejected_slab_given).
 template <bool kSpecular = true, typename RecT = int, bool kIds = false, typename Rej = NoEmitReject,
-          typename KC = ArgConsts>
+          typename KC = ArgConsts, bool kDom = false>
 __device__ __forceinline__ int shade_inv(const TraceArgs& A, const float4* __restrict__ mats,
                                           const float4* __restrict__ tris, RecT* __restrict__ rec_tri,
                                           float* __restrict__ rec_cos, int tid, int hit, float t, Lcg& g, v3& o,
-                                          v3& d, v3& inv, int& k, v3& L, const KC& kc = KC()) {
+                                          v3& d, v3& inv, int& k, v3& L, const KC& kc = KC(),
+                                          uint32_t* dom_at = nullptr) {
     L = v3{0.0f, 0.0f, 0.0f};
     if (hit < 0) return kShadeEnd;  // miss -> 0 (also depth <= 0)
 #ifdef PT_EXP_DUP_SHADE  // measurement only: the hit record and material reads, face-forward and hit point once more
@@ -2026,14 +2073,24 @@ __device__ __forceinline__ int shade_inv(const TraceArgs& A, const float4* __res
     o = add(hp, scale(n, 1e-4f));  // SHIFT_BIAS, render.h:16, 52
     d = nd;
     // bvh.h:157; a hemisphere sample is a unit vector (rcp3_exact), the specular one went through a division
-    if constexpr (RejSlab<Rej>::value) inv = rcp3_exact<!kSpecular>(d);
+    bool fell = true;    // kDom: the wave's verdict on the rays made here (uniform among the lanes here)
+    bool inv_ok = true;  // and the inv half of the slab rule's guard: proven, or tested in the fallback's branch
+    if constexpr (kDom) {
+        static_assert(RejSlab<Rej>::value, "the domain policy goes with the carried inv");
+        inv = rcp3_exact_v<!kSpecular>(d, fell);
+        if (__builtin_expect(fell, 0)) {
+            *dom_at |= kDomMark;
+            inv_ok = finite_nonzero3(inv);
+        }
+    } else if constexpr (RejSlab<Rej>::value) inv = rcp3_exact<!kSpecular>(d);
     if constexpr (Rej::kCompiled) {
         // the next segment (k + 1) is the last and cannot reach an emitter: L stays +0, and k
         // stays too (the record just written is not read: the other lanes' writes issue anyway).
         // No branch per lane: the test is a few compares, the outcome two selects.
         if (Rej::on()) {  // wave-uniform
             bool rej;
-            if constexpr (RejSlab<Rej>::value) rej = Rej::rejected_slab(o, d, inv);
+            if constexpr (kDom) rej = Rej::rejected_slab_given(o, d, inv, inv_ok);
+            else if constexpr (RejSlab<Rej>::value) rej = Rej::rejected_slab(o, d, inv);
             else rej = Rej::rejected(o, d);
             const bool early = ((int)(k + 2 >= depth) & (int)rej) != 0;
             k += early ? 0 : 1;
@@ -2182,8 +2239,14 @@ __device__ __forceinline__ void count_rays_wave(const TraceArgs& A, int lane, un
 #ifndef PT_COUNT_EARLY
 #define PT_COUNT_EARLY 0
 #endif
+// PT_COUNT_DOM (test hook of the scene kernel, through PT_RTC_DEFINES, in place of PT_COUNT_EARLY):
+// the same counter takes the lane-segments that traced a ray carrying the domain mark (DomOnce), i.e.
+// how often the marked branch at the top of the flat body's iteration ran, and for how many lanes.
+#ifndef PT_COUNT_DOM
+#define PT_COUNT_DOM 0
+#endif
 __device__ __forceinline__ void count_early_wave(const TraceArgs& A, int lane, unsigned long long n_early) {
-    if (PT_COUNT_EARLY && lane == 0 && n_early) atomicAdd(A.ctr + 4, n_early);
+    if ((PT_COUNT_EARLY || PT_COUNT_DOM) && lane == 0 && n_early) atomicAdd(A.ctr + 4, n_early);
 }
 
 // The megakernel body of the flat path (scenes with <= 64 leaves).
@@ -2291,6 +2354,14 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
     v3 inv{0, 0, 0};
     constexpr bool kGenInv = kCarry && BoxMask::kCamInvGen;
     v3 next_inv{0, 0, 0};  // kGenInv: 1 / d of the prefetched camera ray (the LDS has no room for it)
+    // kDom (DomOnce, §3.28): bit kDomMark of `at` (and of a stock row's next_at) is the ray's verdict.
+    // kActMask (the same switch, the shared stock): which lanes hold a path is the wave's 64-bit
+    // mask `act`, not a bool per lane, so the wave-level questions about it (who needs a ray, is any
+    // path left, how many rays this segment) are scalar operations; the ballot of a bool that went
+    // through a branch is a select and a compare on the vector port. `active` is then unused.
+    constexpr bool kDom = DomOnce<BoxMask>::value;
+    constexpr bool kActMask = DomOnce<BoxMask>::kMasks && BoxMask::kRayStack;
+    unsigned long long act = 0;
     int k = 0;
     unsigned long long n_rays = 0;  // this wave's segments (wave-uniform)
     unsigned long long n_early = 0;  // PT_COUNT_EARLY: paths the last-ray rule ended
@@ -2323,7 +2394,19 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
 #endif
             next_ray[fresh_tid()] = make_float4(nd.x, nd.y, nd.z, __uint_as_float(gn.s));
             next_at[fresh_tid()] = item;
-            if constexpr (kGenInv) next_inv = rcp3_exact(nd);
+            if constexpr (kGenInv && kDom) {
+                bool fell;  // any float may arrive from the camera: the two-sided, NaN-proof predicate
+                next_inv = rcp3_exact_v<false>(nd, fell);
+                if (__builtin_expect(fell, 0)) next_at[fresh_tid()] = item | kDomMark;  // item < 2^31 (host check)
+            } else if constexpr (kGenInv) next_inv = rcp3_exact(nd);
+        };
+        // a path starts on a camera ray whose inv is made here (PT_CAM_INV=1), row offset in `at`
+        auto start_inv = [&]() {
+            if constexpr (kDom) {
+                bool fell;
+                inv = rcp3_exact_v<false>(d, fell);
+                if (__builtin_expect(fell, 0)) at |= kDomMark;
+            } else inv = rcp3_exact(d);  // bvh.h:157
         };
         if constexpr (BoxMask::kRayStack) {
             // The shared stock (pt_raystack.h): slots [0, count) hold rays, slot s
@@ -2331,7 +2414,10 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
             // sample's radiance goes to its own slab offset, so which lane traces it is free. The
             // generator runs only when the stock cannot serve the lanes without a path, and then
             // lanes count..63 refill every empty slot at once.
-            const unsigned long long need = __ballot(!active);
+            // every wave of the block is full and the loop's exits are wave-uniform: ~act is the ballot
+            unsigned long long need;
+            if constexpr (kActMask) need = ~act;
+            else need = __ballot(!active);
             const int n_need = (int)__popcll(need);
             if (ray_stack_generate(count, n_need, PT_RAY_RESERVE >= 0 ? PT_RAY_RESERVE : A.ray_reserve, dry)) {
                 const bool want = lane >= count;
@@ -2352,7 +2438,14 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
                 const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32),
                                                                 __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
                 const int slot = ray_stack_slot(count, rank);
-                const bool take = !active && slot >= 0;
+                bool take;
+                if constexpr (kActMask) {
+                    const unsigned long long takers = __ballot(slot >= 0) & need;
+                    take = pt_lane_of_mask(takers);
+                    act |= takers;
+                } else {
+                    take = !active && slot >= 0;
+                }
                 // the owning lane's next_inv, fetched by all 64 lanes (a disabled source lane would yield
                 // 0) and kept by the takers: ds_bpermute reads lane (address / 4) mod 64, so a lane that
                 // takes nothing (any slot value) fetches some lane's and drops it
@@ -2367,14 +2460,17 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
                     g.s = __float_as_uint(nr.w);
                     d = v3{nr.x, nr.y, nr.z};
                     if constexpr (kGenInv) inv = ti;
-                    else if constexpr (kCarry) inv = rcp3_exact(d);  // bvh.h:157
+                    else if constexpr (kCarry) start_inv();
                     o = v3{A.pos_x, A.pos_y, A.pos_z};
                     k = 0;
-                    active = true;
+                    if constexpr (!kActMask) active = true;
                 }
                 count = ray_stack_taken(count, n_need);
             }
-            if (ray_stack_done(__any(active), count, dry)) break;
+            bool any_path;
+            if constexpr (kActMask) any_path = act != 0ull;
+            else any_path = __any(active);
+            if (ray_stack_done(any_path, count, dry)) break;
         } else {
             // The per-lane form (PT_RAY_STACK=0): a lane consumes only the ray in its own row, one
             // path ahead, and the generator runs once at least A.regen_thresh lanes of the wave
@@ -2401,7 +2497,7 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
                 g.s = __float_as_uint(nr.w);
                 d = v3{nr.x, nr.y, nr.z};
                 if constexpr (kGenInv) inv = next_inv;
-                else if constexpr (kCarry) inv = rcp3_exact(d);  // bvh.h:157
+                else if constexpr (kCarry) start_inv();
                 o = v3{A.pos_x, A.pos_y, A.pos_z};
                 k = 0;
                 active = true;
@@ -2415,8 +2511,16 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
         // intersecting (render.h:37)
         float t = 0.0f;
         int hit = -1;
-        const bool tr = active && kc.depth(A) > 0;
-        if (kc.depth(A) > 0) n_rays += (unsigned long long)__popcll(__ballot(tr));
+        unsigned long long trm = 0ull;  // kActMask: the lanes that trace, as a mask (unused otherwise)
+        bool tr;
+        if constexpr (kActMask) {
+            trm = kc.depth(A) > 0 ? act : 0ull;
+            tr = pt_lane_of_mask(trm);
+            n_rays += (unsigned long long)__popcll(trm);
+        } else {
+            tr = active && kc.depth(A) > 0;
+            if (kc.depth(A) > 0) n_rays += (unsigned long long)__popcll(__ballot(tr));
+        }
         // bvh.h:157 inv = 1 / d. Waves whose lanes all have finite inv take the IEEE
         // min/max slab test (identical result, see slab_hit_finite).
         if constexpr (!kCarry) inv = rcp3_exact(d, tr);
@@ -2424,7 +2528,28 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
         // with the sign-bit box mask (BoxMask::kSignMask) the wave's plane values must stay
         // finite: |1 / d| <= 2^60 and |o| < 2^60 (scene coordinates < 2^60: the host's
         // condition), so |t| < 2^122; others take the exact walk as zero components do
-        const bool fast = !forced && __all(!tr || (BoxMask::kSignMask ? bounded_ray(o, inv) : all_finite(inv)));
+        bool fast;
+        if constexpr (kDom) {
+            // a lane without a mark has all_finite(inv) proven (DomOnce); a wave with a marked lane
+            // that traces asks as before, and a lane that passes drops its mark (its ray is in the
+            // domain until the next one is made). Lanes without a path may hold a stale mark.
+            bool fin_all = true;
+            // (the ballot of the compare itself, masked by a scalar and: the ballot of a conjunction
+            // with a lane's bool goes through a select and a compare)
+            unsigned long long marked;  // the lanes that trace a marked ray
+            if constexpr (kActMask) marked = __ballot((int)at < 0) & trm;
+            else marked = __ballot(tr && (int)at < 0);
+            if (__builtin_expect(marked != 0ull, 0)) {
+                const bool fin = all_finite(inv);
+                if (fin) at &= ~kDomMark;
+                if constexpr (kActMask) fin_all = (trm & ~__ballot(fin)) == 0ull;
+                else fin_all = __all(!tr || fin);
+                if (PT_COUNT_DOM) n_early += (unsigned long long)__popcll(marked);  // test hook: ctr[4]
+            }
+            fast = !forced && fin_all;
+        } else {
+            fast = !forced && __all(!tr || (BoxMask::kSignMask ? bounded_ray(o, inv) : all_finite(inv)));
+        }
         if (fast && kc.pairs_on(A)) {
             // wave-uniform branch: all 64 lanes take part in the pair queue
             if (PT_PRIO_MASK) __builtin_amdgcn_s_setprio(PT_PRIO_MASK);
@@ -2473,13 +2598,25 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
         int sh = kShadeGo;
         v3 L{0.0f, 0.0f, 0.0f};
         if (PT_PRIO_SHADE) __builtin_amdgcn_s_setprio(PT_PRIO_SHADE);
-        if (active) {
+        bool shading;
+        if constexpr (kActMask) shading = pt_lane_of_mask(act);
+        else shading = active;
+        if (shading) {
             const FlatRecs R = flat_records<BoxMask>(lds4, kc);
-            sh = shade_inv<BoxMask::kSpecular, uint16_t, false, typename BoxMask::EmitRej>(
-                A, mats, tris, R.tri, R.cos, fresh_tid(), hit, t, g, o, d, inv, k, L, kc);
+            sh = shade_inv<BoxMask::kSpecular, uint16_t, false, typename BoxMask::EmitRej, KC, kDom>(
+                A, mats, tris, R.tri, R.cos, fresh_tid(), hit, t, g, o, d, inv, k, L, kc, &at);
         }
         if (PT_PRIO_SHADE) __builtin_amdgcn_s_setprio(0);
-        const bool end = sh != kShadeGo;
+        // kActMask: the ending lanes as a mask, taken where the compare is (a ballot further down, past
+        // the fold's branches, is a select and a compare again), and the fold's lanes from that mask
+        bool end;
+        if constexpr (kActMask) {
+            const unsigned long long endm = __ballot(sh != kShadeGo);
+            end = pt_lane_of_mask(endm);
+            act &= ~endm;  // they leave at the end of this iteration: nothing below reads act
+        } else {
+            end = sh != kShadeGo;
+        }
         if constexpr (BoxMask::EmitRej::kCompiled) {
             // a path ended early still counts its last ray (the reference's BVH::intersect calls)
             const unsigned long long ne = (unsigned long long)__popcll(__ballot(sh == kShadeEndEarly));
@@ -2491,9 +2628,10 @@ __device__ __forceinline__ void trace_body_flat(const TraceArgs& A) {
             if (PT_PRIO_FOLD) __builtin_amdgcn_s_setprio(PT_PRIO_FOLD);
             const FlatRecs R = flat_records<BoxMask>(lds4, kc);
             finish_path<uint16_t, BoxMask::kAlbedoX2, BoxMask::kDarkKnown, BoxMask::kDark>(A, mats, R.tri, R.cos,
-                                                                                        fresh_tid(), k, L, at, kc);
+                                                                                        fresh_tid(), k, L,
+                                                                                        kDom ? at & ~kDomMark : at, kc);
             if (PT_PRIO_FOLD) __builtin_amdgcn_s_setprio(0);
-            active = false;
+            if constexpr (!kActMask) active = false;
         }
         PT_STAMP(st_e)
         PT_STAMP_ADD(0, st_a, st_b)
