@@ -1009,6 +1009,57 @@ int pt_ctx_trace_nee_grad(pt_ctx* ctx, const float* origins, const float* dirs, 
                           const pt_trace_params* params, const pt_trace_grad_io* io, int is_device,
                           pt_nee_grad_stats* stats, const pt_nee_options* options);
 
+/* ---- material gradients of the rendered image along its own camera rays ----------
+ * The two gradients above for the image pt_ctx_render / pt_ctx_render_nee_opt compute: every
+ * sample of a pixel has its own jittered camera ray, and one call covers all of them.
+ *
+ * Arguments. pt_trace_grad_io is reused unchanged with n = the part's pixels (rows * W):
+ * grad_rgb and rgb_out are rows * W * 3 floats in the render's row order; color, emit, grad_color
+ * and grad_emit are num_tris * 3 in the caller's triangle order. pt_params is read as
+ * pt_ctx_render_nee reads it: spp (>= 1), depth (0..PT_MAX_DEPTH), seed and the three part fields;
+ * batch_spp and samples_per_item are not read. `options` as in pt_ctx_trace_nee_opt.
+ *
+ * Sample (p, s) of part-local pixel p is the render's: its LCG starts at
+ * pt_sample_seed(global pixel, s, seed), Camera::get_ray makes its two draws (the y jitter first),
+ * and the path is then trace()'s (pt_*_render_grad) or steps 1-6 of the light-sampling definition
+ * (pt_*_render_nee_grad).
+ *
+ * Forward: rgb_out is the float32 sum over s in order from +0, divided by (float)spp. Without
+ * overrides it is bit-identical to pt_ctx_render / pt_ctx_render_nee_opt for the same camera,
+ * params and part; with overrides it follows the forward rules of pt_ctx_trace_grad /
+ * pt_ctx_trace_nee_grad unchanged (the light table is always the scene's).
+ *
+ * Terms: exactly those sections' per-path terms with w = grad_rgb[p] / (float)spp; the float64
+ * any-order sums, the meaning of `terms` and the rules for +-0 terms are theirs. spp = 1 with a
+ * 1x1 camera adds in k order and is reproducible bit for bit. The gradients of parts 0..N-1 each
+ * cover their own pixels, and their sum is the whole frame's gradient (what a data-parallel fit
+ * over several devices adds up).
+ *
+ * Degenerate cases: a part with no rows is PT_OK and zeroes the gradient outputs; depth 0 zeroes
+ * every output; grad_color or grad_emit without grad_rgb is PT_E_ARG (for a part with pixels).
+ * Stats are filled as by the ray forms, with paths = rows * W * spp. */
+
+/* On the host over the caller's own arrays (no device needed): the camera ray in float32 with each
+ * operation rounded on its own, bit-identical to the device's; sums in double in
+ * (pixel, sample, k) order. */
+int pt_bvh_render_grad(const pt_scene* scene, const pt_camera* cam, const pt_params* params,
+                       const pt_trace_grad_io* io, pt_grad_stats* stats);
+int pt_bvh_render_nee_grad(const pt_scene* scene, const pt_camera* cam, const pt_params* params,
+                           const pt_trace_grad_io* io, pt_nee_grad_stats* stats,
+                           const pt_nee_options* options);
+/* On the context's scene. is_device != 0: every pointer in io is a DEVICE pointer on the context's
+ * device (inputs left untouched), otherwise a host pointer. Launches are cut over samples; the
+ * radiance slab and the in-order sum exist only when rgb_out is asked for, so a gradient-only call
+ * (the backward pass of a fit) writes no radiance. PT_E_RUNAWAY is reported as by pt_ctx_render
+ * (the results are still written). Synchronous; uses buffers of its own, so a progressive sum
+ * stays valid (unlike pt_ctx_render_nee), and an override never reaches the scene or its light
+ * table. */
+int pt_ctx_render_grad(pt_ctx* ctx, const pt_camera* cam, const pt_params* params,
+                       const pt_trace_grad_io* io, int is_device, pt_grad_stats* stats);
+int pt_ctx_render_nee_grad(pt_ctx* ctx, const pt_camera* cam, const pt_params* params,
+                           const pt_trace_grad_io* io, int is_device, pt_nee_grad_stats* stats,
+                           const pt_nee_options* options);
+
 /* Number of rows of part `part_index` for the given partition. */
 int32_t pt_part_rows(int32_t res_y, int32_t part_index, int32_t part_count, int32_t band_rows);
 

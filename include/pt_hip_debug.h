@@ -147,6 +147,11 @@ int pt_debug_flat_lds(int32_t num_tris, int32_t box_tab_bytes, int32_t pair_queu
  * uploads (pt_ctx_set_scene), 2: cached multi-device context sets live, 3: uploads skipped
  * because a cached context already held the same scene. */
 int64_t pt_debug_counter(int32_t which);
+/* Test hook, no device needed: the host form's camera ray (pt_bvh_render_grad) of sample `sample` of
+ * the n part-local pixels first .. first + n - 1 of the part `params` names: org and dir (n * 3
+ * floats each) and states (n), the LCG state after Camera::get_ray's two draws. */
+int pt_debug_host_camera_rays(const pt_camera* cam, const pt_params* params, int32_t sample, int64_t first, int64_t n,
+                              float* org, float* dir, uint32_t* states);
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,8 @@
 //       every segment); a path that ends is unwound with L_{k+1} kept per level, stores its
 //       radiance record, and then runs the throughput pass T_{k+1} = ((2 T_k) color) c, adding
 //       T_k to d emit and ((2 T_k) L_{k+1}) c to d color of bounce k's triangle
+//   pt_grad_cam_kernel<...> the same loop fed from the part's own camera rays (PartRays, pt_paths.h):
+//       the render gradients of DESIGN.md §3.29, grad_rgb indexed by the part-local pixel
 //   pt_grad_gather_kernel   the per-call material array from the scene's and the override rows
 //   pt_grad_split_kernel    the table's rows into the caller's grad_color / grad_emit
 //
@@ -33,8 +35,7 @@
 #include <algorithm>
 
 #include "pt_grad.h"
-#include "pt_raygate.h"
-#include "pt_trace.h"
+#include "pt_paths.h"
 
 namespace pt {
 
@@ -42,34 +43,19 @@ static_assert(kSpecularIterBound == kMaxSpecularIters, "host and device bound of
 
 namespace grad {
 
-struct PathArgs {  // as pt_paths.hip's
-    const float* __restrict__ org;        // m x 3
-    const float* __restrict__ dir;        // m x 3
-    const uint32_t* __restrict__ states;  // m x spp LCG states [ray][sample], or nullptr
-    int* __restrict__ gstack;             // !kLdsStack: [grid][rows][kBlock]
-    int* __restrict__ grec_tri;           // !kLdsRec: [grid][rec][kBlock]
-    float* __restrict__ grec_cos;
-    uint32_t m;                           // rays of this launch
-    uint32_t spp;
-    uint32_t ray_base;                    // index in the call of this launch's first ray (default seeding)
-    int rows;                             // stack rows
-    int force_exact;                      // PT_FORCE_EXACT_SLAB: never the IEEE min/max slab form
-};
-
 struct GradArgs {
     const float* __restrict__ grad_rgb;   // m x 3, or nullptr: forward only
     double* table;                        // [rows][6], global
     const int* __restrict__ rank_tri;     // packed row -> the caller's triangle
     int table_rows;
     uint32_t tab_off;                     // kLdsTab: byte offset of the block's table in LDS
-    float spp_f;                          // (float)spp
+    float spp_f;                          // (float)spp of the call (a render's launches are cut over samples)
     int want_rgb, want_color, want_emit;
 };
 
 }  // namespace grad
 
 using grad::GradArgs;
-using grad::PathArgs;
 
 // `tab` is the block's LDS table or the global one (the kernel's kLdsTab, known at compile time):
 // the hardware add of that address space, ds_add_f64 or global_atomic_add_f64.
@@ -185,8 +171,8 @@ __device__ __forceinline__ uint32_t grad_finish(const TraceArgs& A, const GradAr
     return terms;
 }
 
-template <bool kLdsScene, bool kLdsStack, bool kLdsRec, bool kLdsTab>
-__global__ __launch_bounds__(kBlock) void pt_grad_kernel(TraceArgs A, PathArgs P, GradArgs G) {
+template <class Rays, bool kLdsScene, bool kLdsStack, bool kLdsRec, bool kLdsTab>
+__device__ __forceinline__ void grad_body(const TraceArgs& A, const PathArgs& P, const GradArgs& G) {
     extern __shared__ float4 lds4[];
     const int tid = threadIdx.x;
     const int lane = tid & (kWave - 1);
@@ -234,9 +220,7 @@ __global__ __launch_bounds__(kBlock) void pt_grad_kernel(TraceArgs A, PathArgs P
             claim_item(A, lane, need, pool, alive, item);
             if (need && alive) {  // item < total_items = m * spp
                 const uint32_t sm = fdiv(item, A.div_npix), i = item - sm * P.m;
-                o = v3{P.org[3 * (size_t)i], P.org[3 * (size_t)i + 1], P.org[3 * (size_t)i + 2]};
-                d = v3{P.dir[3 * (size_t)i], P.dir[3 * (size_t)i + 1], P.dir[3 * (size_t)i + 2]};
-                g.s = P.states ? P.states[(size_t)i * P.spp + sm] : pt_sample_seed(P.ray_base + i, sm, A.seed);
+                Rays::load(A, P, i, sm, g, o, d);
                 k = 0;
                 active = true;
             }
@@ -274,6 +258,17 @@ __global__ __launch_bounds__(kBlock) void pt_grad_kernel(TraceArgs A, PathArgs P
             if (!(v == 0.0)) unsafeAtomicAdd(G.table + i, v);  // a NaN goes through
         }
     }
+}
+
+template <bool kLdsScene, bool kLdsStack, bool kLdsRec, bool kLdsTab>
+__global__ __launch_bounds__(kBlock) void pt_grad_kernel(TraceArgs A, PathArgs P, GradArgs G) {
+    grad_body<BufferRays, kLdsScene, kLdsStack, kLdsRec, kLdsTab>(A, P, G);
+}
+
+// The part's own camera rays: item (pixel i, sample A.s_begin + sm), grad_rgb by the part-local pixel.
+template <bool kLdsScene, bool kLdsStack, bool kLdsRec, bool kLdsTab>
+__global__ __launch_bounds__(kBlock) void pt_grad_cam_kernel(TraceArgs A, PathArgs P, GradArgs G) {
+    grad_body<PartRays, kLdsScene, kLdsStack, kLdsRec, kLdsTab>(A, P, G);
 }
 
 // out = the scene's materials with color / emit replaced by the caller-ordered override rows
@@ -320,8 +315,19 @@ GradKernel grad_kernel_t(bool lds_rec, bool lds_tab) {
                    : (lds_tab ? pt_grad_kernel<kLdsScene, kLdsStack, false, true>
                               : pt_grad_kernel<kLdsScene, kLdsStack, false, false>);
 }
+template <bool kLdsScene, bool kLdsStack>
+GradKernel grad_cam_kernel_t(bool lds_rec, bool lds_tab) {
+    return lds_rec ? (lds_tab ? pt_grad_cam_kernel<kLdsScene, kLdsStack, true, true>
+                              : pt_grad_cam_kernel<kLdsScene, kLdsStack, true, false>)
+                   : (lds_tab ? pt_grad_cam_kernel<kLdsScene, kLdsStack, false, true>
+                              : pt_grad_cam_kernel<kLdsScene, kLdsStack, false, false>);
+}
 GradKernel grad_kernel(const GradPlan& p) {
     const bool r = p.walk.lds_rec, t = p.lds_tab;
+    if (p.camera)
+        return p.walk.lds_scene
+                   ? (p.walk.lds_stack ? grad_cam_kernel_t<true, true>(r, t) : grad_cam_kernel_t<true, false>(r, t))
+                   : (p.walk.lds_stack ? grad_cam_kernel_t<false, true>(r, t) : grad_cam_kernel_t<false, false>(r, t));
     return p.walk.lds_scene ? (p.walk.lds_stack ? grad_kernel_t<true, true>(r, t) : grad_kernel_t<true, false>(r, t))
                             : (p.walk.lds_stack ? grad_kernel_t<false, true>(r, t) : grad_kernel_t<false, false>(r, t));
 }
@@ -341,9 +347,11 @@ void grad_place(const QueryScene& sc, int table_rows, size_t lds_usable, int dep
 }
 
 int grad_plan(const QueryScene& sc, int table_rows, size_t lds_usable, int num_cus, int depth, int64_t items,
-              GradPlan& plan) {
+              GradPlan& plan, bool camera) {
     grad_place(sc, table_rows, lds_usable, depth, plan);
-    return walk_grid((const void*)grad_kernel(plan), lds_usable, num_cus, items, plan.walk, "trace_grad");
+    plan.camera = camera ? 1 : 0;
+    return walk_grid((const void*)grad_kernel(plan), lds_usable, num_cus, items, plan.walk,
+                     camera ? "render_grad" : "trace_grad");
 }
 
 int grad_launch(void* stream, const QueryScene& sc, const GradPlan& plan, const GradLaunch& gl) {
@@ -353,6 +361,9 @@ int grad_launch(void* stream, const QueryScene& sc, const GradPlan& plan, const 
     if (l.m <= 0 || l.spp <= 0 || l.depth <= 0 || total >= (1ull << 31))
         return set_error(PT_E_ARG, "trace_grad launch of %d rays x %d samples, depth %d", l.m, l.spp, l.depth);
     if (gl.table_rows <= 0 || !gl.table || !gl.mats) return set_error(PT_E_ARG, "trace_grad launch without a table");
+    if ((plan.camera != 0) != (gl.cam != nullptr) ||
+        (gl.cam && (!gl.prm || !gl.shape || l.m != gl.shape->npix || gl.s_begin < 0 || gl.spp_total < l.spp)))
+        return set_error(PT_E_ARG, "render_grad launch of %d pixels x %d samples from %d", l.m, l.spp, gl.s_begin);
     const int grid = (int)std::min<unsigned long long>((unsigned long long)wp.grid, (total + kBlock - 1) / kBlock);
     // every field shade and claim_item read, as paths_launch (pt_paths.hip) fills them
     TraceArgs A;
@@ -385,6 +396,14 @@ int grad_launch(void* stream, const QueryScene& sc, const GradPlan& plan, const 
     A.static_items = pool.static_items;
     A.static_base = pool.static_base;
     A.acc_chunks = 0;  // no fused accumulation: ctr[2] counts the terms
+    if (gl.cam) {
+        // the fields camera_ray and part_row read, as nee_launch fills them: the items stay numbered
+        // over the part's m = npix pixels
+        fill_camera(A, gl.cam, *gl.shape, gl.prm);
+        A.npix = l.m;
+        A.div_npix = make_fastdiv((uint32_t)l.m);
+        A.s_begin = gl.s_begin;
+    }
 
     PathArgs P{};
     P.org = l.org;
@@ -405,7 +424,7 @@ int grad_launch(void* stream, const QueryScene& sc, const GradPlan& plan, const 
     G.rank_tri = sc.rank_tri;
     G.table_rows = gl.table_rows;
     G.tab_off = (uint32_t)plan.tab_off;
-    G.spp_f = (float)l.spp;
+    G.spp_f = (float)(gl.cam ? gl.spp_total : l.spp);
     G.want_rgb = gl.want_rgb;
     G.want_color = gl.want_color;
     G.want_emit = gl.want_emit;

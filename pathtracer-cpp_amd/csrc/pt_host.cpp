@@ -1435,28 +1435,102 @@ int pt_bvh_trace_nee(const pt_scene* scene, const float* origins, const float* d
     return pt_bvh_trace_nee_opt(scene, origins, dirs, n, prm, rgb_out, stats, nullptr);
 }
 
+// A caller's ray buffer as the host gradient forms' ray source: sample s of ray r is the ray itself
+// with its LCG state, given or by the default seeding (BufferRays of pt_paths.h).
+struct HostBufferRays {
+    const float *origins, *dirs;
+    const pt_trace_params* prm;
+    void load(int64_t r, int s, Lcg& g, v3& o, v3& d) const {
+        g.s = prm->states ? prm->states[(size_t)r * prm->spp + s] : pt_sample_seed((uint32_t)r, (uint32_t)s, prm->seed);
+        o = v3{origins[3 * r], origins[3 * r + 1], origins[3 * r + 2]};
+        d = v3{dirs[3 * r], dirs[3 * r + 1], dirs[3 * r + 2]};
+    }
+};
+
+// Camera::get_ray (camera.h:63-73) on the host for sample s of part-local pixel q, bit for bit the
+// device's camera_ray (pt_trace.h): the LCG starts at pt_sample_seed(global pixel, s, seed), the y
+// jitter is drawn first, and every float32 operation is rounded on its own (no contraction), the
+// normalisation by true square root and divisions. The uniform operands are fill_camera's
+// (pt_launch.hip): v_res / 2, and (-distance) * column z formed once.
+struct HostPartRays {
+    const pt_camera* cam;
+    int32_t W, part_index, parts, band;
+    uint32_t seed;
+    void load(int64_t q, int s, Lcg& g, v3& o, v3& d) const {
+        const int r = (int)(q / W), px = (int)(q - (int64_t)r * W);
+        // row r of the part: band r / band of the part's bands, i.e. band part_index + (r / band) * parts of the image
+        const int py = ((r / band) * parts + part_index) * band + r % band;
+        g.s = pt_sample_seed((uint32_t)(py * W + px), (uint32_t)s, seed);
+        const float jy = g.next01();  // g++ evaluates the y argument first
+        const float jx = g.next01();
+        const float* T = cam->transform;  // rows right, up, -forward; columns feed get_ray's dots
+        const float cx = ((float)px + jx) * cam->cell_size - cam->v_res[0] / 2.0f;
+        const float cy = ((float)py + jy) * cam->cell_size - cam->v_res[1] / 2.0f;
+        const float z0 = -cam->distance * T[6], z1 = -cam->distance * T[7], z2 = -cam->distance * T[8];
+        d = normalize(v3{cx * T[0] + cy * T[3] + z0, cx * T[1] + cy * T[4] + z1, cx * T[2] + cy * T[5] + z2});
+        o = v3{cam->pos[0], cam->pos[1], cam->pos[2]};
+    }
+};
+
+// What the two render-gradient host forms check and derive before their cores: the part's pixels.
+static int host_render_part(const char* who, const pt_camera* cam, const pt_params* prm, const pt_trace_grad_io* io,
+                            HostPartRays& rays, int64_t& npix) {
+    if (!cam) return set_error(PT_E_ARG, "%s: camera is NULL", who);
+    if (!prm) return set_error(PT_E_ARG, "%s: params is NULL", who);
+    if (!io) return set_error(PT_E_ARG, "%s: io is NULL", who);
+    if (prm->spp < 1) return set_error(PT_E_ARG, "%s: spp %d", who, prm->spp);
+    if (prm->depth < 0 || prm->depth > PT_MAX_DEPTH) return set_error(PT_E_ARG, "%s: depth %d", who, prm->depth);
+    const int32_t W = cam->res[0], H = cam->res[1];
+    if (W <= 0 || H <= 0) return set_error(PT_E_ARG, "%s: camera resolution must be positive", who);
+    const int32_t parts = prm->part_count > 0 ? prm->part_count : 1, band = prm->band_rows > 0 ? prm->band_rows : 1;
+    if (prm->part_index < 0 || prm->part_index >= parts) return set_error(PT_E_ARG, "%s: part_index out of range", who);
+    npix = (int64_t)pt_part_rows(H, prm->part_index, parts, band) * W;
+    if (npix > (1ll << 30)) return set_error(PT_E_ARG, "%s: too many pixels for one part", who);
+    rays = HostPartRays{cam, W, prm->part_index, parts, band, prm->seed};
+    return PT_OK;
+}
+
+int pt_debug_host_camera_rays(const pt_camera* cam, const pt_params* prm, int32_t sample, int64_t first, int64_t n, float* org,
+                              float* dir, uint32_t* states) {
+    static const char who[] = "pt_debug_host_camera_rays";
+    const pt_trace_grad_io none{};
+    HostPartRays rays{};
+    int64_t npix = 0;
+    if (int rc = host_render_part(who, cam, prm, &none, rays, npix)) return rc;
+    if (sample < 0 || first < 0 || n < 0 || first + n > npix || !org || !dir || !states)
+        return set_error(PT_E_ARG, "%s: bad argument", who);
+    for (int64_t i = 0; i < n; i++) {
+        Lcg g{0};
+        v3 o, d;
+        rays.load(first + i, sample, g, o, d);
+        org[3 * i] = o.x, org[3 * i + 1] = o.y, org[3 * i + 2] = o.z;
+        dir[3 * i] = d.x, dir[3 * i + 1] = d.y, dir[3 * i + 2] = d.z;
+        states[i] = g.s;
+    }
+    return PT_OK;
+}
+
 // Material gradients of trace() on the host (pt_hip.h: the per-path terms): pt_bvh_trace's walk
 // with colour and emission taken from the override arrays, the unwinding kept per level
 // (L_{k+1}), then the throughput pass. Terms are added in double in (ray, sample, k) order.
-int pt_bvh_trace_grad(const pt_scene* scene, const float* origins, const float* dirs, int64_t n,
-                      const pt_trace_params* prm, const pt_trace_grad_io* io, pt_grad_stats* stats) {
-    const auto t_start = std::chrono::steady_clock::now();
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!prm) return set_error(PT_E_ARG, "pt_bvh_trace_grad: params is NULL");
-    if (!io) return set_error(PT_E_ARG, "pt_bvh_trace_grad: io is NULL");
-    if (n < 0) return set_error(PT_E_ARG, "pt_bvh_trace_grad: n = %lld is negative", (long long)n);
-    if (int prc = trace_params_check("pt_bvh_trace_grad", prm)) return prc;
+// `src`: the ray source (sample s of ray or pixel r; null_rays: a caller's array is NULL); the caller
+// has checked the arguments before the scene.
+extern "C++" {
+template <class Rays>
+static int host_trace_grad(const char* who, const pt_scene* scene, const Rays& src, bool null_rays, int64_t n, int depth,
+                           int spp, const pt_trace_grad_io* io, pt_grad_stats* stats,
+                           std::chrono::steady_clock::time_point t_start) {
     PackedScene ps;
     const int rc = pack_scene(scene, ps);  // pt_scene_validate's checks: the walk cannot leave the arrays
     if (rc) return rc;
     const bool want_grad = io->grad_color || io->grad_emit;
     if (want_grad && !io->grad_rgb && n > 0)
-        return set_error(PT_E_ARG, "pt_bvh_trace_grad: grad_rgb is NULL but a gradient is asked for");
+        return set_error(PT_E_ARG, "%s: grad_rgb is NULL but a gradient is asked for", who);
     const size_t nt = (size_t)scene->num_tris;
     if (io->grad_color) std::fill(io->grad_color, io->grad_color + 3 * nt, 0.0);
     if (io->grad_emit) std::fill(io->grad_emit, io->grad_emit + 3 * nt, 0.0);
     if (n == 0) return PT_OK;
-    if (!origins || !dirs) return set_error(PT_E_ARG, "pt_bvh_trace_grad: NULL argument");
+    if (null_rays) return set_error(PT_E_ARG, "%s: NULL argument", who);
     std::vector<v3> color(nt), emit(nt);
     for (size_t i = 0; i < nt; i++) {
         const pt_material& m = scene->materials[i];
@@ -1467,7 +1541,6 @@ int pt_bvh_trace_grad(const pt_scene* scene, const float* origins, const float* 
     }
     std::vector<int32_t> stack;
     stack.reserve((size_t)ps.stack_size + 1);
-    const int depth = prm->depth, spp = prm->spp;
     const float fs = (float)spp;
     int32_t rec_tri[PT_MAX_DEPTH];
     float rec_cos[PT_MAX_DEPTH];
@@ -1481,9 +1554,9 @@ int pt_bvh_trace_grad(const pt_scene* scene, const float* origins, const float* 
     for (int64_t r = 0; r < n; r++) {
         float sum[3] = {0.0f, 0.0f, 0.0f};
         for (int s = 0; s < spp; s++) {
-            Lcg g{prm->states ? prm->states[(size_t)r * spp + s] : pt_sample_seed((uint32_t)r, (uint32_t)s, prm->seed)};
-            v3 o{origins[3 * r], origins[3 * r + 1], origins[3 * r + 2]};
-            v3 d{dirs[3 * r], dirs[3 * r + 1], dirs[3 * r + 2]};
+            Lcg g{0};
+            v3 o, d;
+            src.load(r, s, g, o, d);
             v3 L{0.0f, 0.0f, 0.0f};
             int k = 0;
             int32_t last = -1;  // the terminal's triangle, -1 a miss
@@ -1568,25 +1641,45 @@ int pt_bvh_trace_grad(const pt_scene* scene, const float* origins, const float* 
                          (unsigned long long)runaway, kSpecularIterBound);
     return PT_OK;
 }
+}  // extern "C++"
+
+int pt_bvh_trace_grad(const pt_scene* scene, const float* origins, const float* dirs, int64_t n,
+                      const pt_trace_params* prm, const pt_trace_grad_io* io, pt_grad_stats* stats) {
+    const auto t_start = std::chrono::steady_clock::now();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    static const char who[] = "pt_bvh_trace_grad";
+    if (!prm) return set_error(PT_E_ARG, "%s: params is NULL", who);
+    if (!io) return set_error(PT_E_ARG, "%s: io is NULL", who);
+    if (n < 0) return set_error(PT_E_ARG, "%s: n = %lld is negative", who, (long long)n);
+    if (int prc = trace_params_check(who, prm)) return prc;
+    return host_trace_grad(who, scene, HostBufferRays{origins, dirs, prm}, !origins || !dirs, n, prm->depth, prm->spp, io,
+                           stats, t_start);
+}
+
+// The same terms along the render's own camera rays: sample s of part-local pixel
+// p is HostPartRays' ray, w = grad_rgb[p] / (float)spp, sums in (pixel, sample, k) order.
+int pt_bvh_render_grad(const pt_scene* scene, const pt_camera* cam, const pt_params* prm, const pt_trace_grad_io* io,
+                       pt_grad_stats* stats) {
+    const auto t_start = std::chrono::steady_clock::now();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    static const char who[] = "pt_bvh_render_grad";
+    HostPartRays rays{};
+    int64_t npix = 0;
+    if (int rc = host_render_part(who, cam, prm, io, rays, npix)) return rc;
+    return host_trace_grad(who, scene, rays, false, npix, prm->depth, prm->spp, io, stats, t_start);
+}
 
 // Material gradients of the light-sampling estimator on the host (pt_hip.h: the per-path
 // quantities and terms): pt_bvh_trace_nee_opt's walk with colour and emission taken from the
 // override arrays and the light table from the scene, a record per bounce (triangle, cosine, the
 // visible light's triangle or -1, g), then the suffix pass R and the throughput pass Tw. Terms are
 // added in double in (ray, sample, k) order.
-int pt_bvh_trace_nee_grad(const pt_scene* scene, const float* origins, const float* dirs, int64_t n,
-                          const pt_trace_params* prm, const pt_trace_grad_io* io, pt_nee_grad_stats* stats,
-                          const pt_nee_options* opt) {
-    const auto t_start = std::chrono::steady_clock::now();
-    if (stats) memset(stats, 0, sizeof(*stats));
-    static const char who[] = "pt_bvh_trace_nee_grad";
-    int mis_mode;
-    if (int orc = pt::nee_options_check(who, opt, &mis_mode)) return orc;
-    const bool mis = mis_mode == PT_NEE_MIS_BALANCE;
-    if (!prm) return set_error(PT_E_ARG, "%s: params is NULL", who);
-    if (!io) return set_error(PT_E_ARG, "%s: io is NULL", who);
-    if (n < 0) return set_error(PT_E_ARG, "%s: n = %lld is negative", who, (long long)n);
-    if (int prc = trace_params_check(who, prm)) return prc;
+// `src`, null_rays: as host_trace_grad's; the caller has checked the options and the arguments before the scene.
+extern "C++" {
+template <class Rays>
+static int host_trace_nee_grad(const char* who, const pt_scene* scene, const Rays& src, bool null_rays, int64_t n, int depth,
+                               int spp, const pt_trace_grad_io* io, pt_nee_grad_stats* stats, bool mis,
+                               std::chrono::steady_clock::time_point t_start) {
     PackedScene ps;
     const int rc = pack_scene(scene, ps);  // pt_scene_validate's checks: the walk cannot leave the arrays
     if (rc) return rc;
@@ -1597,7 +1690,7 @@ int pt_bvh_trace_nee_grad(const pt_scene* scene, const float* origins, const flo
     if (io->grad_color) std::fill(io->grad_color, io->grad_color + 3 * nt, 0.0);
     if (io->grad_emit) std::fill(io->grad_emit, io->grad_emit + 3 * nt, 0.0);
     if (n == 0) return PT_OK;
-    if (!origins || !dirs) return set_error(PT_E_ARG, "%s: NULL argument", who);
+    if (null_rays) return set_error(PT_E_ARG, "%s: NULL argument", who);
     std::vector<v3> color(nt), emit(nt);
     for (size_t i = 0; i < nt; i++) {
         const pt_material& m = scene->materials[i];
@@ -1611,7 +1704,6 @@ int pt_bvh_trace_nee_grad(const pt_scene* scene, const float* origins, const flo
     const int nl = (int)lt.tri.size();
     std::vector<int32_t> stack;
     stack.reserve((size_t)ps.stack_size + 1);
-    const int depth = prm->depth, spp = prm->spp;
     const float fs = (float)spp;
     int32_t rec_tri[PT_MAX_DEPTH], rec_lj[PT_MAX_DEPTH];
     float rec_cos[PT_MAX_DEPTH], rec_g[PT_MAX_DEPTH];
@@ -1625,9 +1717,9 @@ int pt_bvh_trace_nee_grad(const pt_scene* scene, const float* origins, const flo
     for (int64_t r = 0; r < n; r++) {
         float sum[3] = {0.0f, 0.0f, 0.0f};
         for (int s = 0; s < spp; s++) {
-            Lcg g{prm->states ? prm->states[(size_t)r * spp + s] : pt_sample_seed((uint32_t)r, (uint32_t)s, prm->seed)};
-            v3 o{origins[3 * r], origins[3 * r + 1], origins[3 * r + 2]};
-            v3 d{dirs[3 * r], dirs[3 * r + 1], dirs[3 * r + 2]};
+            Lcg g{0};
+            v3 o, d;
+            src.load(r, s, g, o, d);
             v3 T{1.0f, 1.0f, 1.0f}, L{0.0f, 0.0f, 0.0f};
             bool sampled = false;
             int K = 0;                   // bounces recorded
@@ -1771,6 +1863,38 @@ int pt_bvh_trace_nee_grad(const pt_scene* scene, const float* origins, const flo
         return set_error(PT_E_RUNAWAY, "%llu specular rejection loops hit the %d-iteration bound",
                          (unsigned long long)runaway, kSpecularIterBound);
     return PT_OK;
+}
+}  // extern "C++"
+
+int pt_bvh_trace_nee_grad(const pt_scene* scene, const float* origins, const float* dirs, int64_t n,
+                          const pt_trace_params* prm, const pt_trace_grad_io* io, pt_nee_grad_stats* stats,
+                          const pt_nee_options* opt) {
+    const auto t_start = std::chrono::steady_clock::now();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    static const char who[] = "pt_bvh_trace_nee_grad";
+    int mis_mode;
+    if (int orc = pt::nee_options_check(who, opt, &mis_mode)) return orc;
+    if (!prm) return set_error(PT_E_ARG, "%s: params is NULL", who);
+    if (!io) return set_error(PT_E_ARG, "%s: io is NULL", who);
+    if (n < 0) return set_error(PT_E_ARG, "%s: n = %lld is negative", who, (long long)n);
+    if (int prc = trace_params_check(who, prm)) return prc;
+    return host_trace_nee_grad(who, scene, HostBufferRays{origins, dirs, prm}, !origins || !dirs, n, prm->depth, prm->spp, io,
+                               stats, mis_mode == PT_NEE_MIS_BALANCE, t_start);
+}
+
+// The same terms along the render's own camera rays, as pt_bvh_render_grad.
+int pt_bvh_render_nee_grad(const pt_scene* scene, const pt_camera* cam, const pt_params* prm, const pt_trace_grad_io* io,
+                           pt_nee_grad_stats* stats, const pt_nee_options* opt) {
+    const auto t_start = std::chrono::steady_clock::now();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    static const char who[] = "pt_bvh_render_nee_grad";
+    int mis_mode;
+    if (int orc = pt::nee_options_check(who, opt, &mis_mode)) return orc;
+    HostPartRays rays{};
+    int64_t npix = 0;
+    if (int rc = host_render_part(who, cam, prm, io, rays, npix)) return rc;
+    return host_trace_nee_grad(who, scene, rays, false, npix, prm->depth, prm->spp, io, stats, mis_mode == PT_NEE_MIS_BALANCE,
+                               t_start);
 }
 
 // Test hook: FNV-1a (64-bit) of every array and scalar pack_scene produces, so a change to the

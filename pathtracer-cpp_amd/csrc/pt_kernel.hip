@@ -2594,6 +2594,202 @@ int pt_ctx_trace_nee_grad(pt_ctx* c, const float* origins, const float* dirs, in
 }
 }  // extern "C"
 
+// ---------------------------------------------------------------- render gradients
+// Material gradients of the rendered image along the part's own camera rays: the two gradient
+// kernels fed from camera_ray (pt_grad_cam_kernel, pt_nee_grad_cam_kernel). Launches are cut over
+// samples as in pt_ctx_render_nee_opt (PT_RENDER_GRAD_CHUNK, test hook: samples per launch); the
+// table is zeroed once, accumulates across the launches and is split once at the end. The radiance
+// slab and the in-order sum pass exist only with io->rgb_out. The buffers are the caller-ray
+// gradients' own (d_tslab, d_trec, d_tbuf, d_tctr, d_gtab, d_gmats, d_gbuf), never d_accum, so a
+// progressive sum stays valid.
+namespace {
+
+int render_grad_call(const char* who, pt_ctx* c, const pt_camera* cam, const pt_params* prm, const pt_trace_grad_io* io,
+                     int is_device, bool nee, int mis, pt_trace_stats* ts, pt_nee_stats* ns, uint64_t* terms_out,
+                     double* grad_ms_out, int32_t* lds_table_out) {
+    const auto t_start = std::chrono::steady_clock::now();
+    if (!c || !cam || !prm || !io) return set_error(PT_E_ARG, "%s: NULL argument", who);
+    if (prm->spp < 1) return set_error(PT_E_ARG, "%s: spp %d", who, prm->spp);
+    if (prm->depth < 0) return set_error(PT_E_ARG, "%s: depth %d", who, prm->depth);
+    if (!c->have_scene) return set_error(PT_E_ARG, "%s: no scene set", who);
+    PartShape shape;
+    int rc;
+    if ((rc = part_shape(cam, prm, PT_MAX_DEPTH, &shape))) return rc;
+    const int npix = shape.npix, spp = prm->spp;
+    const bool want_grad = io->grad_color || io->grad_emit;
+    if (want_grad && !io->grad_rgb && npix > 0)
+        return set_error(PT_E_ARG, "%s: grad_rgb is NULL but a gradient is asked for", who);
+    if ((rc = ctx_ready(c))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const int32_t T = c->meta.num_tris;  // the caller's triangles (one tri_idx position each)
+    const size_t g_bytes = 3 * sizeof(double) * (size_t)T;
+    const size_t nval = 3 * (size_t)npix;
+    unsigned long long h_ctr[kTraceCounters] = {};
+    if (npix == 0 || prm->depth == 0) {  // no ray is traced: every output is +0 (+0 / spp)
+        if ((rc = zero_output(c, io->grad_color, g_bytes, is_device)) || (rc = zero_output(c, io->grad_emit, g_bytes, is_device)) ||
+            (rc = zero_output(c, io->rgb_out, sizeof(float) * nval, is_device)))
+            return rc;
+        if (is_device) HIP_TRY(hipStreamSynchronize(c->stream));
+        fill_trace_stats(ts, nullptr, true, h_ctr, (uint64_t)npix * (uint64_t)spp, 0, 0, 0, t_start);
+        if (ns) nee_light_stats(ns, c, h_ctr);
+        return PT_OK;
+    }
+    const bool want_rgb = io->rgb_out != nullptr;
+    // samples per launch: npix * c < 2^31 items, and with a slab its budget
+    int64_t c_max = std::min<int64_t>(spp, ((1ll << 31) - 1) / npix);
+    if (want_rgb)
+        c_max = std::min<int64_t>(c_max, (int64_t)(std::min<size_t>(batch_bytes_budget(c->device, false), (size_t)4 << 30) /
+                                                   (sizeof(float) * nval)));
+    if (const char* gc = hook_env("PT_RENDER_GRAD_CHUNK"))
+        if (*gc) c_max = std::min<int64_t>(c_max, strtoll(gc, nullptr, 10));
+    c_max = std::max<int64_t>(c_max, 1);
+    const QueryScene sc = query_scene(c);
+    GradPlan gplan;
+    NeeGradPlan nplan;
+    NeeLights lights{};
+    const int64_t items = (int64_t)npix * c_max;
+    if (nee) {
+        if ((rc = nee_lights(c, &lights))) return rc;
+        if ((rc = nee_grad_plan(sc, T, c->lds_usable, c->num_cus, prm->depth, items, nplan, true))) return rc;
+    } else {
+        if ((rc = grad_plan(sc, T, c->lds_usable, c->num_cus, prm->depth, items, gplan, true))) return rc;
+    }
+    const WalkPlan& walk = nee ? nplan.walk : gplan.walk;
+    if (walk.stack_ints > 0 && (rc = ensure(&c->d_qstack, &c->qstack_ints, walk.stack_ints))) return rc;
+    if (walk.rec_words > 0 && (rc = ensure(&c->d_trec, &c->trec_words, 2 * walk.rec_words))) return rc;
+    if (want_rgb && (rc = ensure(&c->d_tslab, &c->tslab_floats, nval * (size_t)c_max))) return rc;
+    // the running sum of the in-order pass, then (host pointers) the image's staging
+    if (want_rgb && (rc = ensure(&c->d_tbuf, &c->tbuf_floats, 2 * nval))) return rc;
+    if ((rc = trace_counters(c))) return rc;
+    if ((rc = ensure(&c->d_gtab, &c->gtab_doubles, 12 * (size_t)T))) return rc;  // table, then the split outputs
+    // the per-call materials, then (light sampling) every light's emission
+    if ((rc = ensure(&c->d_gmats, &c->gmats_f4, 2 * (size_t)T + (size_t)lights.count))) return rc;
+    f4* const lemit = reinterpret_cast<f4*>(c->d_gmats) + 2 * (size_t)T;
+    // host pointers: [color 3T][emit 3T][grad_rgb 3 npix]
+    const float *d_color = io->color, *d_emit = io->emit, *d_grgb = want_grad ? io->grad_rgb : nullptr;
+    if (!is_device) {
+        if ((rc = ensure(&c->d_gbuf, &c->gbuf_floats, 6 * (size_t)T + nval))) return rc;
+        if (io->color) {
+            HIP_TRY(hipMemcpyAsync(c->d_gbuf, io->color, 3 * sizeof(float) * (size_t)T, hipMemcpyHostToDevice, c->stream));
+            d_color = c->d_gbuf;
+        }
+        if (io->emit) {
+            HIP_TRY(hipMemcpyAsync(c->d_gbuf + 3 * (size_t)T, io->emit, 3 * sizeof(float) * (size_t)T, hipMemcpyHostToDevice,
+                                   c->stream));
+            d_emit = c->d_gbuf + 3 * (size_t)T;
+        }
+        if (want_grad) {
+            HIP_TRY(hipMemcpyAsync(c->d_gbuf + 6 * (size_t)T, io->grad_rgb, sizeof(float) * nval, hipMemcpyHostToDevice, c->stream));
+            d_grgb = c->d_gbuf + 6 * (size_t)T;
+        }
+    }
+    EventPair evg, evs;
+    if ((rc = evg.create()) || (rc = evs.create())) return rc;
+    HIP_TRY(hipEventRecord(evg.a, c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_gtab, 0, 6 * sizeof(double) * (size_t)T, c->stream));
+    const f4* mats = sc.mats;
+    if (io->color || io->emit) {
+        if ((rc = grad_gather_mats(c->stream, sc, d_color, d_emit, reinterpret_cast<f4*>(c->d_gmats)))) return rc;
+        mats = reinterpret_cast<const f4*>(c->d_gmats);
+    }
+    if (nee && (rc = nee_grad_gather_lights(c->stream, lights, d_emit, lemit))) return rc;
+    HIP_TRY(hipEventRecord(evg.b, c->stream));
+    PathsLaunch l;
+    if ((rc = paths_launch_base(c, 0, prm->depth, prm->seed, want_rgb ? c->d_tslab : nullptr, c->d_tctr,
+                                walk.rec_words > 0 ? c->d_trec : nullptr, 0, l)))
+        return rc;
+    l.m = npix;
+    GradLaunch gl{};
+    NeeGradLaunch ngl{};
+    gl.mats = ngl.mats = mats;
+    ngl.lemit = lemit;
+    gl.grad_rgb = ngl.grad_rgb = d_grgb;
+    gl.table = ngl.table = c->d_gtab;
+    gl.table_rows = ngl.table_rows = T;
+    gl.want_rgb = ngl.want_rgb = want_rgb ? 1 : 0;
+    gl.want_color = ngl.want_color = io->grad_color ? 1 : 0;
+    gl.want_emit = ngl.want_emit = io->grad_emit ? 1 : 0;
+    ngl.mis = mis;
+    gl.cam = ngl.cam = cam;
+    gl.prm = ngl.prm = prm;
+    gl.shape = ngl.shape = &shape;
+    gl.spp_total = ngl.spp_total = spp;
+    float* const accum = c->d_tbuf;
+    float* const dst = want_rgb ? (is_device ? io->rgb_out : c->d_tbuf + nval) : nullptr;
+    double kernel_ms = 0, reduce_ms = 0;
+    int launches = 0;
+    LaunchTimer timer;
+    if ((rc = timer.create())) return rc;
+    for (int s0 = 0; s0 < spp; s0 += (int)c_max) {
+        const int sc_n = (int)std::min<int64_t>(c_max, spp - s0);
+        l.spp = sc_n;
+        gl.p = ngl.p = l;
+        gl.s_begin = ngl.s_begin = s0;
+        HIP_TRY(hipMemsetAsync(c->d_tctr, 0, sizeof(unsigned long long), c->stream));  // work head only
+        if ((rc = timer.mark(0, c->stream))) return rc;
+        if ((rc = nee ? nee_grad_launch(c->stream, sc, nplan, ngl, lights) : grad_launch(c->stream, sc, gplan, gl))) return rc;
+        if ((rc = timer.mark(1, c->stream))) return rc;
+        if (want_rgb) {  // the pixel's samples in order from +0, then / spp on the last launch (image.h:27-31, 37-40)
+            hipLaunchKernelGGL(pt_accumulate_kernel, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->d_tslab,
+                               accum, dst, npix, sc_n, s0 == 0 ? 1 : 0, s0 + sc_n == spp ? 1 : 0, 0, (float)spp,
+                               (const uint32_t*)nullptr, 0);
+            HIP_TRY(hipGetLastError());
+        }
+        if ((rc = timer.mark(2, c->stream))) return rc;
+        launches++;
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if ((rc = timer.add(&kernel_ms, &reduce_ms))) return rc;
+    }
+    // the table's rows into the caller's two arrays
+    HIP_TRY(hipEventRecord(evs.a, c->stream));
+    if (want_grad) {
+        double* o_color = io->grad_color ? (is_device ? io->grad_color : c->d_gtab + 6 * (size_t)T) : nullptr;
+        double* o_emit = io->grad_emit ? (is_device ? io->grad_emit : c->d_gtab + 9 * (size_t)T) : nullptr;
+        if ((rc = grad_split_table(c->stream, c->d_gtab, T, o_color, o_emit))) return rc;
+        if (!is_device) {
+            if (o_color) HIP_TRY(hipMemcpyAsync(io->grad_color, o_color, g_bytes, hipMemcpyDeviceToHost, c->stream));
+            if (o_emit) HIP_TRY(hipMemcpyAsync(io->grad_emit, o_emit, g_bytes, hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    HIP_TRY(hipEventRecord(evs.b, c->stream));
+    if (want_rgb && !is_device) HIP_TRY(hipMemcpyAsync(io->rgb_out, dst, sizeof(float) * nval, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(h_ctr, c->d_tctr, sizeof(h_ctr), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    float gather_ms = 0, split_ms = 0;
+    HIP_TRY(hipEventElapsedTime(&gather_ms, evg.a, evg.b));
+    HIP_TRY(hipEventElapsedTime(&split_ms, evs.a, evs.b));
+    if (terms_out) *terms_out = h_ctr[2];
+    if (grad_ms_out) *grad_ms_out = (double)gather_ms + (double)split_ms;
+    if (lds_table_out) *lds_table_out = nee ? nplan.lds_tab : gplan.lds_tab;
+    fill_trace_stats(ts, &walk, true, h_ctr, (uint64_t)npix * (uint64_t)spp, kernel_ms, reduce_ms, launches, t_start);
+    if (ns) nee_light_stats(ns, c, h_ctr);
+    return runaway_result(h_ctr[3]);
+}
+
+}  // namespace
+
+extern "C" {
+
+int pt_ctx_render_grad(pt_ctx* c, const pt_camera* cam, const pt_params* prm, const pt_trace_grad_io* io, int is_device,
+                       pt_grad_stats* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    return render_grad_call("pt_ctx_render_grad", c, cam, prm, io, is_device, false, PT_NEE_MIS_NONE,
+                            stats ? &stats->trace : nullptr, nullptr, stats ? &stats->terms : nullptr,
+                            stats ? &stats->grad_ms : nullptr, stats ? &stats->lds_table : nullptr);
+}
+
+int pt_ctx_render_nee_grad(pt_ctx* c, const pt_camera* cam, const pt_params* prm, const pt_trace_grad_io* io, int is_device,
+                           pt_nee_grad_stats* stats, const pt_nee_options* opt) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    int mis;
+    if (int orc = nee_options_check("pt_ctx_render_nee_grad", opt, &mis)) return orc;
+    return render_grad_call("pt_ctx_render_nee_grad", c, cam, prm, io, is_device, true, mis,
+                            stats ? &stats->nee.trace : nullptr, stats ? &stats->nee : nullptr, stats ? &stats->terms : nullptr,
+                            stats ? &stats->grad_ms : nullptr, stats ? &stats->lds_table : nullptr);
+}
+
+}  // extern "C"
+
 // ---------------------------------------------------------------- adaptive sampling
 // pt_ctx_render_converge whose later rounds go only to the pixels that still miss the criterion:
 // dense rounds through moments_range, then per-pixel rounds through the kernels of pt_adaptive.hip

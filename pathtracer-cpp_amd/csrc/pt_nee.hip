@@ -2,7 +2,7 @@
 // over the binary child-pair walk (gfx950).
 //
 //   pt_nee_kernel<kLdsScene, kLdsStack>      the caller's buffer of rays (BufferRays, pt_paths.h)
-//   pt_nee_cam_kernel<kLdsScene, kLdsStack>  the part's own camera rays (PartRays)
+//   pt_nee_cam_kernel<kLdsScene, kLdsStack>  the part's own camera rays (PartRays, pt_paths.h)
 //   pt_nee_mis_kernel, pt_nee_mis_cam_kernel the same two with the balance-heuristic weights
 //                                            (PT_NEE_MIS_BALANCE; kMis in shade_nee)
 //
@@ -53,15 +53,6 @@ struct NeeArgs {
     unsigned long long* __restrict__ nctr;    // [0] shadow segments, [1] light draws
     int nlights;
     float area, kA;
-};
-
-// Sample A.s_begin + sm of pixel i of the part: the render's camera ray (camera_ray seeds at the
-// global pixel index and makes Camera::get_ray's two draws; A holds the camera and partition fields).
-struct PartRays {
-    __device__ __forceinline__ static void load(const TraceArgs& A, const PathArgs&, uint32_t i, uint32_t sm, Lcg& g, v3& o,
-                                                v3& d) {
-        camera_ray(A, (int)i, A.s_begin + (int)sm, g, o, d);
-    }
 };
 
 __device__ __forceinline__ v3 f4_xyz(float4 a) { return v3{a.x, a.y, a.z}; }

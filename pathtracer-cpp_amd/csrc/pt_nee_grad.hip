@@ -9,10 +9,12 @@
 //       ascending k, adding the terms; R_{k+1} of bounce k is unwound again from the records for
 //       every k (the records hold four words a level, R three: pt_grad.hip's deep-path form, here
 //       at every depth — at depth 5 that is at most 6 more suffix steps a path, against its walks).
+//   pt_nee_grad_cam_kernel<...>  the same loop fed from the part's own camera rays (PartRays,
+//       pt_paths.h): the render gradients of DESIGN.md §3.29, grad_rgb indexed by the part-local pixel
 //   pt_nee_grad_lights_kernel  the per-call emission of every light: its override row, or the table's
 //
 // The weights are a runtime choice (NeeGradArgs::mis, uniform): the two estimators share every
-// kernel, so there are 16 instantiations and not 32. The walk, the samplers and the light choice are
+// kernel, so there are 16 instantiations per ray source and not 32. The walk, the samplers and the light choice are
 // the forward estimator's, untouched: they depend on geometry, roughness and the LCG only. The
 // fields of NeeGradArgs are re-read from the kernarg segment where they are used (ng_args): held in
 // SGPRs across the walk they spilled (31-42 SGPRs, and a private segment in half the kernels).
@@ -57,7 +59,7 @@ struct NeeGradArgs {
     int levels;                             // record levels per lane
     int table_rows;
     uint32_t tab_off;                       // kLdsTab: byte offset of the block's table in LDS
-    float spp_f;                            // (float)spp
+    float spp_f;                            // (float)spp of the call (a render's launches are cut over samples)
     int want_rgb, want_color, want_emit;
 };
 
@@ -267,8 +269,8 @@ __device__ __forceinline__ uint32_t nee_grad_finish(const float4* __restrict__ m
 
 // __launch_bounds__'s second argument (waves per SIMD): left to itself the register allocator stops
 // at 83-87 VGPRs, 5 waves; asked for 6 it fits 78-79 with no spill (make resource-usage-nee-grad).
-template <bool kLdsScene, bool kLdsStack, bool kLdsRec, bool kLdsTab>
-__global__ __launch_bounds__(kBlock, 6) void pt_nee_grad_kernel(TraceArgs A, PathArgs P, NeeGradArgs N) {
+template <class Rays, bool kLdsScene, bool kLdsStack, bool kLdsRec, bool kLdsTab>
+__device__ __forceinline__ void nee_grad_body(const TraceArgs& A, const PathArgs& P, const NeeGradArgs& N) {
     extern __shared__ float4 lds4[];
     const int tid = threadIdx.x;
     const int lane = tid & (kWave - 1);
@@ -321,7 +323,7 @@ __global__ __launch_bounds__(kBlock, 6) void pt_nee_grad_kernel(TraceArgs A, Pat
             claim_item(A, lane, need, pool, alive, item);
             if (need && alive) {  // item < total_items = m * spp
                 const uint32_t sm = fdiv(item, A.div_npix), i = item - sm * P.m;
-                BufferRays::load(A, P, i, sm, g, o, d);
+                Rays::load(A, P, i, sm, g, o, d);
                 k = 0;
                 T = v3{1.0f, 1.0f, 1.0f};
                 L = v3{0.0f, 0.0f, 0.0f};
@@ -389,6 +391,17 @@ __global__ __launch_bounds__(kBlock, 6) void pt_nee_grad_kernel(TraceArgs A, Pat
     }
 }
 
+template <bool kLdsScene, bool kLdsStack, bool kLdsRec, bool kLdsTab>
+__global__ __launch_bounds__(kBlock, 6) void pt_nee_grad_kernel(TraceArgs A, PathArgs P, NeeGradArgs N) {
+    nee_grad_body<BufferRays, kLdsScene, kLdsStack, kLdsRec, kLdsTab>(A, P, N);
+}
+
+// The part's own camera rays: item (pixel i, sample A.s_begin + sm), grad_rgb by the part-local pixel.
+template <bool kLdsScene, bool kLdsStack, bool kLdsRec, bool kLdsTab>
+__global__ __launch_bounds__(kBlock, 6) void pt_nee_grad_cam_kernel(TraceArgs A, PathArgs P, NeeGradArgs N) {
+    nee_grad_body<PartRays, kLdsScene, kLdsStack, kLdsRec, kLdsTab>(A, P, N);
+}
+
 // out[j] = the emission light j is evaluated at
 __global__ __launch_bounds__(kBlock) void pt_nee_grad_lights_kernel(const float4* __restrict__ lgeom,
                                                                     const int32_t* __restrict__ ltri,
@@ -415,8 +428,19 @@ NeeGradKernel nee_grad_kernel_t(bool lds_rec, bool lds_tab) {
                    : (lds_tab ? pt_nee_grad_kernel<kLdsScene, kLdsStack, false, true>
                               : pt_nee_grad_kernel<kLdsScene, kLdsStack, false, false>);
 }
+template <bool kLdsScene, bool kLdsStack>
+NeeGradKernel nee_grad_cam_kernel_t(bool lds_rec, bool lds_tab) {
+    return lds_rec ? (lds_tab ? pt_nee_grad_cam_kernel<kLdsScene, kLdsStack, true, true>
+                              : pt_nee_grad_cam_kernel<kLdsScene, kLdsStack, true, false>)
+                   : (lds_tab ? pt_nee_grad_cam_kernel<kLdsScene, kLdsStack, false, true>
+                              : pt_nee_grad_cam_kernel<kLdsScene, kLdsStack, false, false>);
+}
 NeeGradKernel nee_grad_kernel(const NeeGradPlan& p) {
     const bool r = p.walk.lds_rec, t = p.lds_tab;
+    if (p.camera)
+        return p.walk.lds_scene
+                   ? (p.walk.lds_stack ? nee_grad_cam_kernel_t<true, true>(r, t) : nee_grad_cam_kernel_t<true, false>(r, t))
+                   : (p.walk.lds_stack ? nee_grad_cam_kernel_t<false, true>(r, t) : nee_grad_cam_kernel_t<false, false>(r, t));
     return p.walk.lds_scene ? (p.walk.lds_stack ? nee_grad_kernel_t<true, true>(r, t) : nee_grad_kernel_t<true, false>(r, t))
                             : (p.walk.lds_stack ? nee_grad_kernel_t<false, true>(r, t) : nee_grad_kernel_t<false, false>(r, t));
 }
@@ -426,8 +450,9 @@ NeeGradKernel nee_grad_kernel(const NeeGradPlan& p) {
 // nee_plan's placement with 2 x (depth - 1) of place_walk's two-word record rows (four words a
 // level), then the table while it fits the same cap beside them (grad_place's rule).
 int nee_grad_plan(const QueryScene& sc, int table_rows, size_t lds_usable, int num_cus, int depth, int64_t items,
-                  NeeGradPlan& plan) {
+                  NeeGradPlan& plan, bool camera) {
     plan.levels = std::max(0, depth - 1);
+    plan.camera = camera ? 1 : 0;
     place_walk_hooked(sc.num_nodes, sc.num_tris, sc.tree_depth, 5, 2 * plan.levels, lds_usable, true, plan.walk);
     const size_t cap = std::min<size_t>(64 * 1024, lds_usable / 2);
     const size_t off = (plan.walk.lds_bytes + 15) / 16 * 16;
@@ -435,7 +460,8 @@ int nee_grad_plan(const QueryScene& sc, int table_rows, size_t lds_usable, int n
     plan.lds_tab = !hook_off("PT_GRAD_LDS") && table_rows > 0 && lds_round(off + tab_b) <= cap;
     plan.tab_off = plan.lds_tab ? off : 0;
     if (plan.lds_tab) plan.walk.lds_bytes = off + tab_b;
-    return walk_grid((const void*)nee_grad_kernel(plan), lds_usable, num_cus, items, plan.walk, "trace_nee_grad");
+    return walk_grid((const void*)nee_grad_kernel(plan), lds_usable, num_cus, items, plan.walk,
+                     camera ? "render_nee_grad" : "trace_nee_grad");
 }
 
 int nee_grad_launch(void* stream, const QueryScene& sc, const NeeGradPlan& plan, const NeeGradLaunch& gl,
@@ -449,6 +475,9 @@ int nee_grad_launch(void* stream, const QueryScene& sc, const NeeGradPlan& plan,
         return set_error(PT_E_ARG, "trace_nee_grad launch of %d rays x %d samples, depth %d", l.m, l.spp, l.depth);
     if (gl.table_rows <= 0 || !gl.table || !gl.mats) return set_error(PT_E_ARG, "trace_nee_grad launch without a table");
     if (!wp.lds_rec && plan.levels > 0 && !l.grec) return set_error(PT_E_ARG, "trace_nee_grad launch without a record buffer");
+    if ((plan.camera != 0) != (gl.cam != nullptr) ||
+        (gl.cam && (!gl.prm || !gl.shape || l.m != gl.shape->npix || gl.s_begin < 0 || gl.spp_total < l.spp)))
+        return set_error(PT_E_ARG, "render_nee_grad launch of %d pixels x %d samples from %d", l.m, l.spp, gl.s_begin);
     const int grid = (int)std::min<unsigned long long>((unsigned long long)wp.grid, (total + kBlock - 1) / kBlock);
     TraceArgs A;
     PathArgs P;
@@ -456,6 +485,14 @@ int nee_grad_launch(void* stream, const QueryScene& sc, const NeeGradPlan& plan,
     A.mats = reinterpret_cast<const float4*>(gl.mats);
     A.dark = 0;
     A.acc_chunks = 0;  // no fused accumulation: ctr[2] counts the terms
+    if (gl.cam) {
+        // the fields camera_ray and part_row read, as nee_launch fills them: the items stay numbered
+        // over the part's m = npix pixels
+        fill_camera(A, gl.cam, *gl.shape, gl.prm);
+        A.npix = l.m;
+        A.div_npix = make_fastdiv((uint32_t)l.m);
+        A.s_begin = gl.s_begin;
+    }
     NeeGradArgs N{};
     N.cdf = lights.cdf;
     N.ltri = lights.tri;
@@ -473,7 +510,7 @@ int nee_grad_launch(void* stream, const QueryScene& sc, const NeeGradPlan& plan,
     N.levels = plan.levels;
     N.table_rows = gl.table_rows;
     N.tab_off = (uint32_t)plan.tab_off;
-    N.spp_f = (float)l.spp;
+    N.spp_f = (float)(gl.cam ? gl.spp_total : l.spp);
     N.want_rgb = gl.want_rgb;
     N.want_color = gl.want_color;
     N.want_emit = gl.want_emit;

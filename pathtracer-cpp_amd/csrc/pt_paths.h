@@ -4,6 +4,8 @@
 //
 //   BufferRays  item -> a ray of the caller's buffer (pt_paths_kernel, pt_paths.hip)
 //   ListRays    item -> camera_ray of a listed pixel of the part (pt_adaptive_kernel, pt_adaptive.hip)
+//   PartRays    item -> camera_ray of a pixel of the part (the light-sampling render, pt_nee.hip, and
+//               the render gradients, pt_grad.hip and pt_nee_grad.hip)
 //
 // and the host's filling of the loop's arguments (paths_args, pt_paths.hip).
 #pragma once
@@ -48,6 +50,15 @@ struct ListRays {
     __device__ __forceinline__ static void load(const TraceArgs& A, const PathArgs& P, uint32_t i, uint32_t sm, Lcg& g,
                                                 v3& o, v3& d) {
         camera_ray(A, (int)P.list[i], A.s_begin + (int)sm, g, o, d);
+    }
+};
+
+// Sample A.s_begin + sm of pixel i of the part: the render's camera ray (camera_ray seeds at the
+// global pixel index and makes Camera::get_ray's two draws; A holds the camera and partition fields).
+struct PartRays {
+    __device__ __forceinline__ static void load(const TraceArgs& A, const PathArgs&, uint32_t i, uint32_t sm, Lcg& g, v3& o,
+                                                v3& d) {
+        camera_ray(A, (int)i, A.s_begin + (int)sm, g, o, d);
     }
 };
 

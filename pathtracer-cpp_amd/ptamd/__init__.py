@@ -355,6 +355,28 @@ class BVH:
                                           C.byref(st), _nee_options(mis)))
         return res, st.as_dict()
 
+    def render_grad(self, camera: "Camera", grad_img, samples: int, depth: int, seed: int = PT_SEED, color=None, emit=None,
+                    want=GRAD_WANT, light_sampling: bool = False, mis: bool = False):
+        """Renderer.render_grad on the host for the whole frame (pt_bvh_render_grad /
+        pt_bvh_render_nee_grad; no device needed): the camera ray stated on the host, bit for bit the
+        device's, and the same per-path terms, summed in double in (pixel, sample, bounce) order."""
+        if mis and not light_sampling:
+            raise ValueError("mis needs light_sampling")
+        ref = _SceneRef(self)
+        W, H = camera.res
+        prm = _lib.pt_params(samples, depth, seed, 0, 1, 1, 0, 0)
+        io, res, _keep = _grad_io_host(len(self.triangles), H * W, grad_img, color, emit, want)
+        if light_sampling:
+            st = _lib.pt_nee_grad_stats()
+            check(lib().pt_bvh_render_nee_grad(C.byref(ref.s), C.byref(camera.c), C.byref(prm), C.byref(io), C.byref(st),
+                                               _nee_options(mis)))
+        else:
+            st = _lib.pt_grad_stats()
+            check(lib().pt_bvh_render_grad(C.byref(ref.s), C.byref(camera.c), C.byref(prm), C.byref(io), C.byref(st)))
+        if "rgb" in res:
+            res["rgb"] = res["rgb"].reshape(H, W, 3)
+        return res, st.as_dict()
+
     @classmethod
     def from_scene(cls, scene) -> "BVH":
         b = cls()
@@ -830,6 +852,64 @@ class Renderer:
         fn = lib().pt_ctx_trace_nee_grad
         return self._trace_grad(lambda *args: fn(*args, _nee_options(mis)), _lib.pt_nee_grad_stats(), origins, directions,
                                 grad_rgb, depth, samples, seed, states, color, emit, want)
+
+    def render_grad(self, camera: Camera, grad_img, samples: int, depth: int, seed: int = PT_SEED, part_index: int = 0,
+                    part_count: int = 1, band_rows: int = 1, color=None, emit=None, want=GRAD_WANT,
+                    light_sampling: bool = False, mis: bool = False):
+        """The image render() (or, with `light_sampling`, render_nee(mis=mis)) gives for this part at
+        (optionally) changed materials, and its exact gradient with respect to every triangle's
+        color and emit_color (pt_ctx_render_grad / pt_ctx_render_nee_grad; the contract is in
+        include/pt_hip.h): every sample of a pixel runs along its own jittered camera ray, in one
+        call. `grad_img`: (rows, W, 3) float32 dLoss/d image in render()'s row order, needed for the
+        gradients; `color` / `emit`, `want` and the results are trace_grad's, with "rgb" of shape
+        (rows, W, 3). Without "rgb" in `want` no radiance is written (the backward pass of a fit).
+        The gradients of the parts of a frame sum to the frame's. numpy arrays go through host
+        pointers; contiguous float32 torch tensors on this context's device (every array argument
+        then, at least one of them) through device pointers, under the rule of the device-pointer
+        paths. Unlike render_nee the call leaves this context's running sum valid."""
+        if mis and not light_sampling:
+            raise ValueError("mis needs light_sampling")
+        W, H = camera.res
+        rows = self.part_rows(H, part_index, part_count, band_rows)
+        n, T = rows * W, self.num_tris
+        prm = _lib.pt_params(samples, depth, seed, part_index, part_count, band_rows, 0, 0)
+        if light_sampling:
+            st = _lib.pt_nee_grad_stats()
+            call = lambda io, dev: lib().pt_ctx_render_nee_grad(self.h, C.byref(camera.c), C.byref(prm), C.byref(io), dev,
+                                                                C.byref(st), _nee_options(mis))
+        else:
+            st = _lib.pt_grad_stats()
+            call = lambda io, dev: lib().pt_ctx_render_grad(self.h, C.byref(camera.c), C.byref(prm), C.byref(io), dev,
+                                                            C.byref(st))
+        given = [x for x in (grad_img, color, emit) if x is not None]
+        if any(_is_tensor(x) for x in given):
+            import torch
+            want = _grad_want(want)
+            io, res, f32 = _lib.pt_trace_grad_io(), {}, []
+            for key, val, cnt in (("color", color, 3 * T), ("emit", emit, 3 * T), ("grad_rgb", grad_img, 3 * n)):
+                if val is not None:
+                    f32.append((val, cnt))
+                    if _is_tensor(val):
+                        setattr(io, key, val.data_ptr())
+            self._device_tensors(f32, "grad_img, color and emit must be contiguous float32 tensors of rows x W x 3 / "
+                                 "num_tris x 3 elements on the context's device", dtype=torch.float32)
+            if ("color" in want or "emit" in want) and grad_img is None:
+                raise ValueError("grad_img is needed for the gradients")
+            dev = torch.device("cuda", self.device)
+            if "rgb" in want:
+                res["rgb"] = torch.empty((rows, W, 3), dtype=torch.float32, device=dev)
+                io.rgb_out = res["rgb"].data_ptr()
+            for k in ("color", "emit"):
+                if k in want:
+                    res[k] = torch.empty((T, 3), dtype=torch.float64, device=dev)
+                    setattr(io, "grad_" + k, res[k].data_ptr())
+            check(call(io, 1))
+            return res, st.as_dict()
+        io, res, _keep = _grad_io_host(T, n, grad_img, color, emit, want)
+        check(call(io, 0))
+        if "rgb" in res:
+            res["rgb"] = res["rgb"].reshape(rows, W, 3)
+        return res, st.as_dict()
 
     def _trace_grad(self, fn, st, origins, directions, grad_rgb, depth, samples, seed, states, color, emit, want):
         """pt_ctx_trace_grad or pt_ctx_trace_nee_grad (`fn`, stats `st`): the tensor path and the numpy path."""

@@ -39,6 +39,8 @@ EXPORTED = (
     "pt_scene_lights", "pt_bvh_trace_nee", "pt_ctx_trace_nee", "pt_ctx_render_nee",
     "pt_bvh_trace_nee_opt", "pt_ctx_trace_nee_opt", "pt_ctx_render_nee_opt",
     "pt_bvh_trace_nee_grad", "pt_ctx_trace_nee_grad",
+    "pt_bvh_render_grad", "pt_bvh_render_nee_grad", "pt_ctx_render_grad", "pt_ctx_render_nee_grad",
+    "pt_debug_host_camera_rays",
 )
 PT_NEE_MIS_NONE, PT_NEE_MIS_BALANCE = 0, 1
 PT_MAX_DEVICES = 16
@@ -423,6 +425,18 @@ def lib() -> C.CDLL:
                                                 C.POINTER(pt_nee_options)]
             L.pt_ctx_trace_nee_grad.argtypes = [P, P, P, C.c_int64, C.POINTER(pt_trace_params), C.POINTER(pt_trace_grad_io),
                                                 C.c_int, C.POINTER(pt_nee_grad_stats), C.POINTER(pt_nee_options)]
+        if hasattr(L, "pt_ctx_render_grad"):  # absent from older builds used in A/B runs
+            L.pt_bvh_render_grad.argtypes = [C.POINTER(pt_scene), C.POINTER(pt_camera), C.POINTER(pt_params),
+                                             C.POINTER(pt_trace_grad_io), C.POINTER(pt_grad_stats)]
+            L.pt_bvh_render_nee_grad.argtypes = [C.POINTER(pt_scene), C.POINTER(pt_camera), C.POINTER(pt_params),
+                                                 C.POINTER(pt_trace_grad_io), C.POINTER(pt_nee_grad_stats),
+                                                 C.POINTER(pt_nee_options)]
+            L.pt_ctx_render_grad.argtypes = [P, C.POINTER(pt_camera), C.POINTER(pt_params), C.POINTER(pt_trace_grad_io),
+                                             C.c_int, C.POINTER(pt_grad_stats)]
+            L.pt_ctx_render_nee_grad.argtypes = [P, C.POINTER(pt_camera), C.POINTER(pt_params), C.POINTER(pt_trace_grad_io),
+                                                 C.c_int, C.POINTER(pt_nee_grad_stats), C.POINTER(pt_nee_options)]
+            L.pt_debug_host_camera_rays.argtypes = [C.POINTER(pt_camera), C.POINTER(pt_params), C.c_int32, C.c_int64,
+                                                    C.c_int64, P, P, P]
         if hasattr(L, "pt_debug_rccl_failover"):  # test hooks (absent from older builds used in A/B runs)
             L.pt_debug_rccl_failover.argtypes = [C.c_int32, C.c_int32, P]
         if hasattr(L, "pt_debug_rtc_cache"):

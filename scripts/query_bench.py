@@ -37,6 +37,17 @@ anything is timed. Then the variance over --seeds independent seeds (one sample 
 summed over the light's triangles and of d color of the wall triangle with the largest gradient,
 for trace_nee_grad and for trace_grad, and variance x wall ms of either. Writes <out>/<scene>.json
 (default profiles/nee_grad).
+
+--mode render_grad: one Renderer.render_grad call (pt_ctx_render_grad / pt_ctx_render_nee_grad,
+device buffers, a seeded dLoss/d image, --spp samples a pixel) beside what it replaces, the
+per-sample loop: the AOV rays of sample s, pt_sample_seed stepped twice, trace_grad(samples=1) with
+grad_rgb / spp, the float64 tables and the float32 image added on the device. Both estimators (plain,
+and light sampling with the weights), each timed as forward + gradients and as gradients only; the
+wall time of each, --reps times after a warm-up, in turn, twice, as median / min / max. The forward
+images are compared bit for bit and the gradients to 1e-9 relative before anything is timed. With a
+library that lacks the new entry points (PT_LIB = an older build) only the loop is timed: its
+run-to-run spread on the code the call replaces. Writes <out>/<scene>.json (default
+profiles/render_grad).
 """
 import argparse
 import json
@@ -373,6 +384,84 @@ def bench_nee_grad_scene(name, res, warmup, reps, seeds, depth=5, spp=1):
                          "nee_grad_over_trace_grad": ratio}}
 
 
+def bench_render_grad_scene(name, res, warmup, reps, depth=5, spp=4):
+    import torch
+    import ptamd
+    from ptamd import scenes
+    sc = scenes.cornell((res, res)) if name == "cornell" else scenes.sphere_in_cornell(int(name[len("sphere"):]), (res, res))
+    bvh = ptamd.BVH.from_scene(sc)
+    cam = ptamd.Camera.from_spec(sc.camera)
+    r = ptamd.Renderer(0)
+    r.set_scene(bvh)
+    r.prepare()
+    dev = torch.device("cuda", 0)
+    n = res * res
+    G = torch.from_numpy(np.random.default_rng(5).uniform(-1, 1, (res, res, 3)).astype(np.float32)).to(dev)
+    gs = (G / np.float32(spp)).reshape(n, 3).contiguous()
+    have_call = hasattr(ptamd.lib(), "pt_ctx_render_grad")
+    last = {}
+
+    def loop(mode, want_rgb):
+        want = (("rgb",) if want_rgb else ()) + ("color", "emit")
+        states = torch.from_numpy(camera_states(n, spp, 1).view(np.int32)).to(dev)
+        acc = color = emit = None
+        for s in range(spp):
+            a, _ = r.aov(cam, sample=s, channels=("ray",), device=True)
+            ray = a["ray"].reshape(n, 6)
+            o, d = ray[:, 0:3].contiguous(), ray[:, 3:6].contiguous()
+            st = states[:, s].contiguous()
+            if mode == "plain":
+                x, _ = r.trace_grad(o, d, gs, depth, states=st, want=want)
+            else:
+                x, _ = r.trace_nee_grad(o, d, gs, depth, states=st, want=want, mis=True)
+            color = x["color"] if color is None else color + x["color"]
+            emit = x["emit"] if emit is None else emit + x["emit"]
+            if want_rgb:
+                acc = x["rgb"] if acc is None else acc + x["rgb"]
+        torch.cuda.synchronize()
+        last["loop"] = {"color": color, "emit": emit, "rgb": (acc / np.float32(spp)).reshape(res, res, 3) if want_rgb else None}
+
+    def call(mode, want_rgb):
+        want = (("rgb",) if want_rgb else ()) + ("color", "emit")
+        x, st = r.render_grad(cam, G, spp, depth, want=want, light_sampling=mode != "plain", mis=mode != "plain")
+        last["call"], last["call_st"] = x, st
+
+    def timed_wall(f, *a):
+        for _ in range(warmup):
+            f(*a)
+        wall = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            f(*a)
+            wall.append((time.perf_counter() - t0) * 1e3)
+        return spread(wall)
+
+    lines, checks = {}, {}
+    for mode in ("plain", "nee_mis"):
+        if have_call:
+            loop(mode, True)
+            call(mode, True)
+            a, b = last["loop"], last["call"]
+            assert torch.equal(a["rgb"].view(torch.int32), b["rgb"].view(torch.int32)), f"{name} {mode}: forward images differ"
+            rel = max(float(((a[k] - b[k]).abs().max() / b[k].abs().max())) for k in ("color", "emit"))
+            assert rel < 1e-9, f"{name} {mode}: gradients differ by {rel}"
+            checks[mode] = {"rgb_bits_equal": True, "grad_max_rel_diff": rel, "terms": last["call_st"]["terms"],
+                            "rays": last["call_st"]["rays"], "launches": last["call_st"]["launches"],
+                            "placement": {k: last["call_st"][k] for k in ("lds_scene", "lds_stack", "lds_records", "lds_table")}}
+        for _ in range(2):  # in turn, twice
+            for want_rgb in (True, False):
+                tag = f"{mode}_{'forward_and_gradients' if want_rgb else 'gradients_only'}"
+                lines.setdefault("loop_" + tag, []).append(timed_wall(loop, mode, want_rgb))
+                if have_call:
+                    lines.setdefault("call_" + tag, []).append(timed_wall(call, mode, want_rgb))
+    med = {k: spread([row["median"] for row in v])["median"] for k, v in lines.items()}
+    ratios = {k[len("call_"):]: med[k] / med["loop_" + k[len("call_"):]] for k in med if k.startswith("call_")}
+    r.close()
+    return {"scene": sc.name, "tris": len(sc.tris), "res": [res, res], "depth": depth, "spp": spp, "warmup": warmup, "reps": reps,
+            "device": torch.cuda.get_device_name(0), "library_has_render_grad": have_call, "checks": checks, "wall_ms": lines,
+            "wall_ms_median": med, "call_over_loop": ratios}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--scenes", default="cornell,sphere223")
@@ -380,19 +469,22 @@ def main():
     ap.add_argument("--min-ms", type=float, default=1000.0, help="kernel time per line")
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--mode", choices=("query", "trace", "grad", "nee_grad"), default="query")
-    ap.add_argument("--reps", type=int, default=9, help="--mode nee_grad: timed calls per line")
+    ap.add_argument("--mode", choices=("query", "trace", "grad", "nee_grad", "render_grad"), default="query")
+    ap.add_argument("--reps", type=int, default=9, help="--mode nee_grad, render_grad: timed calls per line")
+    ap.add_argument("--spp", type=int, default=4, help="--mode render_grad: samples per pixel")
     ap.add_argument("--seeds", type=int, default=32, help="--mode nee_grad: independent seeds of the variance")
     ap.add_argument("--out", default=None, help="default profiles/query, profiles/paths with --mode trace, profiles/grad with --mode grad, "
-                    "profiles/nee_grad with --mode nee_grad")
+                    "profiles/nee_grad with --mode nee_grad, profiles/render_grad with --mode render_grad")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", {"trace": "paths", "grad": "grad", "nee_grad": "nee_grad"}.get(args.mode, "query"))
+        args.out = os.path.join(ROOT, "profiles", {"trace": "paths", "grad": "grad", "nee_grad": "nee_grad", "render_grad": "render_grad"}.get(args.mode, "query"))
     if args.mode in ("trace", "grad"):
         os.environ["PT_TEST_HOOKS"] = "1"  # PT_FLAT / PT_WIDE pick the yardstick's kernel, PT_GRAD_LDS the table form
     os.makedirs(args.out, exist_ok=True)
     for name in args.scenes.split(","):
-        if args.mode == "nee_grad":
+        if args.mode == "render_grad":
+            res = bench_render_grad_scene(name, args.res, args.warmup, args.reps, spp=args.spp)
+        elif args.mode == "nee_grad":
             res = bench_nee_grad_scene(name, args.res, args.warmup, args.reps, args.seeds)
         elif args.mode == "grad":
             res = bench_grad_scene(name, args.res, args.min_ms, args.warmup)
