@@ -766,9 +766,14 @@ int pt_ctx_trace(pt_ctx* ctx, const float* origins, const float* dirs, int64_t n
  *
  * Sum: each destination is the sum of its float32 terms in float64, in any order (so within
  * gamma_{N-1} sum|t| of the exact sum of its N terms); a call with n = 1, spp = 1 adds in k order
- * and is reproducible bit for bit. Non-finite rays or materials make the affected destinations
- * non-finite; nothing else is promised for them. A scene's dark-path shortcut never drops a
- * grad_emit term (a dark path still carries T_k != 0). */
+ * and is reproducible bit for bit. A term that is +-0 is counted in `terms` and leaves its
+ * destination as it is. Non-finite rays, materials or upstream gradients, and products that
+ * overflow, give non-finite terms; per destination and channel the sum then has the class that
+ * float64 addition gives in any order (N float32 terms cannot overflow a double): NaN if a term
+ * is NaN or if +inf and -inf both occur, +inf if only +inf occurs, -inf if only -inf occurs. A
+ * channel all of whose terms are finite keeps its bound whatever the other channels and
+ * destinations hold. A scene's dark-path shortcut never drops a grad_emit term (a dark path still
+ * carries T_k != 0). */
 typedef struct pt_trace_grad_io {
     const float* color;     /* optional, num_tris*3: albedo to evaluate at, caller's triangle order; NULL = the scene's */
     const float* emit;      /* optional, num_tris*3: emit_color to evaluate at; NULL = the scene's        */
